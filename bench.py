@@ -31,6 +31,14 @@ products are ordered per-block sums exchanged with RCCL all-gathers.  The host
 communicator is the build's own TCP rendezvous (sgvamp-py_amd/comm.py), torch
 is never imported.
 
+A plain run sets up, warms up, times ``--steps`` steps and prints the line;
+its roofline figures come from the timers the library keeps anyway.  ``--full``
+adds the legs that take runs of their own after the timed steps: the CPU
+baseline (``cpu_baseline``) and the device's streaming-read probe
+(``roofline.box_stream_GBs``); both are null in a plain line.
+``--dump-outputs DIR`` writes the last timed step's results as .npy files (same
+arguments, same inputs: two builds can be compared output for output).
+
 Prints ONE JSON line on rank 0 (other output goes to stderr).
 """
 import argparse
@@ -71,7 +79,15 @@ def parse():
                    help="one LD matrix per cohort (the reference's per-rank ld_fpaths_list[rank], "
                         "src/main.py:173,199-202) instead of K cohorts sharing one")
     p.add_argument("--seed", type=int, default=2025)
-    p.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the legs that take runs of their own: "
+                        "the CPU baseline (--cpu-baseline) and the streaming-read probe "
+                        "(--read-bw); a plain run skips both")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last one computed (xhat1, every "
+                        "cohort's r1, the step's scalars) as DIR/<name>.npy in float64")
+    p.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto",
+                   help="with --full: auto = the CPU baseline leg on one rank")
     p.add_argument("--cpu-blocks", type=int, default=4,
                    help="LD blocks of the CPU-baseline sample (see cpu_baseline)")
     p.add_argument("--cpu-iters", type=int, default=3)
@@ -90,8 +106,8 @@ def parse():
                    help="seconds the device idles after set-up, before the warm-up steps "
                         "(clock/thermal studies: the set-up's generator kernels heat the chip)")
     p.add_argument("--read-bw", type=int, default=1,
-                   help="1: after the timed steps, measure the GPU's streaming-read rate "
-                        "(roofline.box_stream_GBs)")
+                   help="with --full, 1: after the timed steps, measure the GPU's streaming-read "
+                        "rate (roofline.box_stream_GBs)")
     p.add_argument("--dry-run", action="store_true",
                    help="start the ranks and report each one's rank/device as one JSON line, "
                         "without touching the GPU (checks the launch)")
@@ -334,6 +350,43 @@ def cpu_baseline(eng, args, ref_flags, recs, x0):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6   # all the .npy files of --dump-outputs together (< 64 MB)
+
+
+def dump_outputs(path, eng, comm, rec):
+    """--dump-outputs: what the last timed step computed, as a caller of
+    VAMP.step finds it -- xhat1 (the denoised estimate the step leaves on the
+    device: the xhat output file's content before its 1/sqrt(Nt)), every
+    cohort's r1 (K x M) and the step's scalars (rec: gamw, gam1, gam2, alpha1,
+    alpha2 per cohort, lam, the CG iteration counts) -- one float64 .npy each,
+    written by rank 0.  When the arrays together exceed the budget (K = 8 at
+    M = 1e6) the long ones are cut to a seeded sample of their elements: the
+    same ascending indices in every run."""
+    import hip_backend as hb
+
+    def whole(which, k=0):
+        loc = eng.get_vector(which, k)
+        return np.concatenate(comm.allgather(loc)) if comm.Get_size() > 1 else loc
+
+    arrays = {"xhat1": whole(hb.VEC_XHAT1),
+              "r1": np.stack([whole(hb.VEC_R1, k) for k in range(eng.K)])}
+    if rec is not None:
+        arrays["scalars"] = np.array([np.asarray(rec[n], dtype=np.float64).ravel() for n in
+                                      ("gamw", "gam1", "gam2", "alpha1", "alpha2")])
+        arrays["lam"] = np.atleast_1d(np.asarray(rec["lam"], dtype=np.float64))
+        arrays["cg_iters"] = np.asarray(rec["cg_iters"], dtype=np.float64)
+    if comm.Get_rank() != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    frac = min(1.0, DUMP_BUDGET_BYTES / float(sum(a.nbytes for a in arrays.values())))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if frac < 1.0 and a.size > 4096:
+            idx = np.random.RandomState(20250).choice(a.size, int(a.size * frac), replace=False)
+            a = a.ravel()[np.sort(idx)]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def flags_label(args, prior):
     """The reference CLI flags (src/main.py:27-50) this run uses, naming every
     one that differs from the CLI's default."""
@@ -462,10 +515,12 @@ def main():
     ci = eng.comm_info()
     ci.update(rank=rank, host_wait_ms_per_step=xs["host_wait_ms"] / args.steps)
     ci_all = comm.allgather(ci) if world > 1 else [ci]
-    # this box's own streaming-read rate (after the timed region; context only:
-    # the roofline peak stays the guide's 8 TB/s); the slowest rank's
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, comm, recs[-1] if recs else None)
+    # --full: the device's own streaming-read rate (after the timed region; context
+    # only: the roofline peak stays the chip's 8 TB/s); the slowest rank's
     box_bw = None
-    if args.read_bw:
+    if args.full and args.read_bw:
         try:
             bw = eng.read_bw(8 << 30, 5)
         except Exception as e:  # noqa: BLE001 -- context only: the bench line stays valid
@@ -525,6 +580,7 @@ def main():
         "ms_per_step": dt / steps * 1e3,
         "higher_is_better": True,
         "scaling": "strong",
+        "full": bool(args.full),
         "vs_baseline": None,
         "dtype": "f64",
         "data": ("synthetic: windowed LD (simulate.windowed_ld), r = R x0 + N(0,1), 5%% causal, "
@@ -632,7 +688,7 @@ def main():
         "effective_ld_gbps_end_to_end": passes * ld_bytes_total / dt / 1e9,
         "cg_iters_per_step": [r["cg_iters"] for r in recs],
     }
-    if rank == 0 and world == 1 and args.cpu_baseline == "auto" and not args.band:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline == "auto" and not args.band:
         log("[bench] cpu baseline ...")
         result["cpu_baseline"] = cpu_baseline(eng, args, dict(flags, **run), recs, x0)
     else:

@@ -4,6 +4,8 @@ import json
 import os
 import sys
 
+import numpy as np
+
 from tests.conftest import ROOT
 
 sys.path.insert(0, ROOT)
@@ -51,6 +53,71 @@ def test_northstar_and_c2_summaries_present():
              for d in sums.values()}
     assert ("k_sym_pass", 2.0e10) in kinds          # C2, K = 1
     assert ("k_sym_mfma", 6.4e10) in kinds          # north star, M = 1e6, K = 4
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    """The legs that take runs of their own (CPU baseline, read probe) are behind
+    --full; --steps and --warmup set the loops' counts."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+    assert a.cpu_baseline == "auto" and a.read_bw == 1      # --full runs both by default
+
+
+class _OneRank:
+    def Get_size(self):
+        return 1
+
+    def Get_rank(self):
+        return 0
+
+
+class _Vectors:
+    """get_vector of a stand-in engine: xhat1 and K cohorts' r1 of M markers."""
+
+    def __init__(self, K, M):
+        import hip_backend as hb
+
+        rs = np.random.RandomState(5)
+        self.K, self.M = K, M
+        self.v = {(hb.VEC_XHAT1, 0): rs.normal(size=M)}
+        for k in range(K):
+            self.v[(hb.VEC_R1, k)] = rs.normal(size=M)
+
+    def get_vector(self, which, k=0):
+        return self.v[(which, k)].copy()
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    import hip_backend as hb
+
+    K, M = 3, 5000
+    eng = _Vectors(K, M)
+    rec = dict(gamw=[1.0, 2.0, 3.0], gam1=[4.0, 5.0, 6.0], gam2=np.array([7.0, 8.0, 9.0]),
+               alpha1=[0.1, 0.2, 0.3], alpha2=[0.4, 0.5, 0.6], lam=0.25,
+               cg_iters=[[3, 4], [5, 6], [7, 8]])
+    bench.dump_outputs(str(tmp_path / "a"), eng, _OneRank(), rec)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == ["cg_iters", "lam", "r1", "scalars", "xhat1"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    np.testing.assert_array_equal(got["xhat1"], eng.v[(hb.VEC_XHAT1, 0)])
+    np.testing.assert_array_equal(got["r1"], np.stack([eng.v[(hb.VEC_R1, k)] for k in range(K)]))
+    assert got["scalars"].shape == (5, K) and got["scalars"][2].tolist() == [7.0, 8.0, 9.0]
+    assert got["lam"].tolist() == [0.25] and got["cg_iters"].tolist() == rec["cg_iters"]
+    # over the budget: the same seeded sample of the long arrays in every run
+    whole = sum(a.nbytes for a in got.values())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", whole // 2)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), eng, _OneRank(), rec)
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert sum(a.nbytes for a in b.values()) <= whole // 2 + 8 * 64
+    assert b["r1"].ndim == 1 and b["r1"].size == int(K * M * ((whole // 2) / float(whole)))
+    assert np.isin(b["r1"], got["r1"]).all() and b["scalars"].shape == (5, K)
+    for n in b:
+        np.testing.assert_array_equal(b[n], np.load(tmp_path / "c" / (n + ".npy")))
 
 
 def test_workload_label_names_non_default_flags():

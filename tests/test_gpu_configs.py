@@ -211,8 +211,8 @@ def test_band_bench_over_ranks_equals_one_rank(tmp_path):
     piece each, a halo all-gather per pass) write output files bitwise equal to
     one rank's, and the line names the band workload."""
     flags = ["--band", "150000,500", "--K", "2"]
-    one = _bench(tmp_path / "one", *flags)
-    two = _bench(tmp_path / "two", *flags, gpus=2)
+    one = _bench(tmp_path / "one", *flags, "--dump-outputs", str(tmp_path / "dump1"))
+    two = _bench(tmp_path / "two", *flags, "--dump-outputs", str(tmp_path / "dump2"), gpus=2)
     _log("band", "one rank", one["cg_iters_per_step"], one["roofline"]["frac"])
     assert one["config"]["band"] == "150000,500" and one["config"]["ld_blocks"] >= 2
     assert "windowed LD" in one["config"]["workload"] and one["cpu_baseline"] is None
@@ -222,6 +222,20 @@ def test_band_bench_over_ranks_equals_one_rank(tmp_path):
     assert len([f for f in files if f.endswith(".bin")]) == 3 * (2 + 1)
     for f in files:
         assert (tmp_path / "one" / f).read_bytes() == (tmp_path / "two" / f).read_bytes(), f
+    # --dump-outputs: the last timed step (iteration 2) as float64 .npy files, the
+    # same from one rank and from two; xhat1 is what that step's xhat file holds
+    assert one["full"] is False and one["roofline"]["box_stream_GBs"] is None
+    names = sorted(os.listdir(tmp_path / "dump1"))
+    assert names == ["cg_iters.npy", "lam.npy", "r1.npy", "scalars.npy", "xhat1.npy"]
+    d1 = {n[:-4]: np.load(tmp_path / "dump1" / n) for n in names}
+    for n in d1:
+        assert d1[n].dtype == np.float64
+        np.testing.assert_array_equal(d1[n], np.load(tmp_path / "dump2" / (n + ".npy")), err_msg=n)
+    assert d1["xhat1"].shape == (150000,) and d1["r1"].shape == (2, 150000)
+    assert d1["scalars"].shape == (5, 2) and np.isfinite(d1["xhat1"]).all()
+    assert d1["cg_iters"].tolist() == one["cg_iters_per_step"][-1]
+    np.testing.assert_array_equal(d1["xhat1"] / np.sqrt(2 * 10000),
+                                  np.fromfile(tmp_path / "one" / "bench_xhat_it_2.bin"))
 
 
 def _gate_50(nblk, size, K, tmp_path, its=50, ref_algebra=False):

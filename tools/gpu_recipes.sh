@@ -25,7 +25,7 @@ case $recipe in
     SEL=${*:-tests}
     exec_steps=("gputests_$T:${SUITE_LIMIT:-1000}:SGV_TEST_TIMES=gpurun_out/testtimes_$T.txt SGV_GATE_LOG=gpurun_out/gates_$T.log python -u -m pytest $SEL -m gpu -x -q -p no:cacheprovider --timeout 900 --timeout-method thread -rs --durations=40"
                 "smoke_$T:300:python -c 'import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")'"
-                "bench_$T:300:python bench.py")
+                "bench_$T:300:python bench.py --full")
     [ -n "$NO_BENCH" ] && unset 'exec_steps[2]' 
     tools/gpu_steps.sh "${exec_steps[@]}" ;;
   trace)
@@ -65,7 +65,7 @@ case $recipe in
       python -c "import json; d=json.load(open('${o}_$name.json')); r=d['roofline']; c=d.get('compute_roofline'); print(json.dumps(dict(config='$name', value=round(d['value'],3), ms_per_step=round(d['ms_per_step'],3), ms_pass=round(r['avg_launch_ms'],4), frac=round(r['frac'],4), passes=round(d['ld_passes_per_step'],2), stream=r.get('box_stream_GBs'), mfma_frac=(round(c['frac'],4) if c else None), xchg=d['exchange']['allgathers_per_step'])))" | tee -a ${o}.jsonl
     }
     Q="--cpu-baseline off --read-bw 0"
-    run ns 600 --cpu-baseline off
+    run ns 600 --full --cpu-baseline off
     run c2 400 --blocks 8 --block-size 25000 --K 1 $Q
     run c3 400 --blocks 8 --block-size 25000 --K 4 $Q
     run c4 400 --K 1 $Q
