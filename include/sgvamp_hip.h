@@ -133,8 +133,8 @@ int sgv_set_ld_block_csr(sgv_ctx* ctx, int ld, int blk_local, const int64_t* ind
  * reference fixtures the carried form agrees as closely (tests/). */
 int sgv_set_rs_recurrence(sgv_ctx* ctx, int on);
 /* Packed passes with at least nc_min right-hand sides run on the f64 matrix
- * cores (v_mfma_f64_16x16x4f64); fewer run on the VALU.  0 = never.  Default 3
- * (env SGV_MFMA_MIN).  Results agree to rounding, not bitwise, across the two. */
+ * cores (v_mfma_f64_16x16x4f64); fewer run on the VALU.  0 = never.  Default 3.
+ * Results agree to rounding, not bitwise, across the two. */
 int sgv_set_mfma_min(sgv_ctx* ctx, int nc_min);
 /* CG and EM-loop drivers (scipy iterative.py:397-422; src/sgvamp.py:250-257):
  * on (default) the CG's stop test, beta and alpha, and the EM prior loop's

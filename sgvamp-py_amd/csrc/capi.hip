@@ -472,7 +472,7 @@ extern "C" void sgv_destroy(sgv_ctx* c) {
   if (c->ev_den) (void)hipEventDestroy(c->ev_den);
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
-  for (auto* v : {&c->pending, &c->xpending, &c->gpending})
+  for (auto* v : {&c->pending, &c->xpending, &c->gpending, &c->empending})
     for (auto& pr : *v) {
       (void)hipEventDestroy(pr.first);
       (void)hipEventDestroy(pr.second);

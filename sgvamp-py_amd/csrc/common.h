@@ -139,6 +139,17 @@ struct SymPanel {
 struct SymStrip {
   int32_t it0, npan, slot, ncmax;
 };
+// Wide strips (k_sym_mfma_wide): the same SymStrip over 1,024-column chunks
+// c0 = 256 cls + 1024 k (cls = 0..3) and the panels g = cls, cls + 4, ..., c0 /
+// 256 of a dense-triangle block; the items are the class-0 (1,024-column)
+// items, colpart slots are 1,024 wide.  The column sums of a panel's rows sit
+// in the strips of four chunks: the one starting k panels before it holds them
+// at row offset 256 k -- colpart slots [sb[k], se[k])
+constexpr int MFW_CW = 1024;
+struct SymPanelW {
+  SymPanel p;
+  int32_t sb[4], se[4];
+};
 
 // band walks (band_walk.hip): a workgroup walks panels p0 .. p0 + np - 1 (one
 // block, consecutive; entries of the walk panel table) with a ring of R = the
@@ -380,6 +391,15 @@ bool strip_pk_paired(int nc);
 hipError_t launch_sym_mfma(int nc, const SymStrip* d_strips, int nstrips, const SymItem* d_sitems,
                            const PassArgs& pa, const double* d_pk, double* rowpart,
                            double* colpart, bool ragged, int pair, hipStream_t st);
+// wide strips (3-8 columns, dense-triangle blocks): rowpart per (panel,
+// 1,024-column chunk) item, colpart slots 1,024 wide; idle_exit: waves wholly
+// past a strip's last column leave at once
+hipError_t launch_sym_mfma_wide(int nc, const SymStrip* d_strips, int nstrips,
+                                const SymItem* d_sitems, const PassArgs& pa, const double* d_pk,
+                                double* rowpart, double* colpart, bool idle_exit, hipStream_t st);
+hipError_t launch_sym_finalize_wide(int nc, const SymPanelW* d_panels, int npanels,
+                                    const PassArgs& pa, const double* rowpart,
+                                    const double* colpart, double* partials, hipStream_t st);
 // band walks (NC <= 8, band_walk.hip): the walks, then the head panels' finalize
 hipError_t launch_band_walk(int nc, const SymWalk* d_walks, int nwalks, const SymPanel* d_panels,
                             const SymItem* d_items, const double* d_pk, int64_t pk_rows,

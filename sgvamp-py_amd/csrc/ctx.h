@@ -54,6 +54,24 @@ struct LdCoupling {
 };
 
 // launch tables of one LD matrix (rebuilt when a block's storage changes)
+// Strip tables of one MFMA strip kernel family over some of a plan's packed
+// blocks (build_strips): strips in dispatch order, their items in strip order,
+// the blocks' panels with their colpart slot ranges (wide: SymPanelW), and the
+// block groups (contiguous blocks): group g's strips are d_strips[gs[g] ..
+// gs[g+1]), its panels [gp[g] .. gp[g+1])
+struct StripSet {
+  SymStrip* d_strips = nullptr;
+  SymItem* d_sitems = nullptr;
+  SymPanel* d_panels = nullptr;
+  SymPanelW* d_wpanels = nullptr;
+  int nstrips = 0, npanels = 0, nsitems = 0;
+  int nslots_items = 0;        // rowpart item slots spanned (the items' class table)
+  bool ragged = false;         // some strip item is narrower than its strip (band blocks)
+  int pair = 0;                // k_sym_mfma_pair by the tail model (1) / forced (2)
+  int ngrp = 1;
+  std::vector<int> gs, gp;
+};
+
 struct LdPlan {
   bool valid = false;
   RowGroup* d_rg = nullptr;    // dense blocks
@@ -64,19 +82,16 @@ struct LdPlan {
   int nitems[4] = {0, 0, 0, 0};
   SymPanel* d_panels[4] = {nullptr, nullptr, nullptr, nullptr};
   int npanels = 0;
-  // MFMA pass: strips (dispatch order), their class-1 items in strip order, and
-  // the class-1 panels with their strip ranges
-  SymStrip* d_strips = nullptr;
-  SymItem* d_sitems = nullptr;
-  SymPanel* d_spanels = nullptr;
-  int nstrips = 0;
-  bool ragged = false;         // some strip item is narrower than its strip (band blocks)
-  int pair = 0;                // k_sym_mfma_pair for 3-4 columns (1) / 3-8 (2) (build_strips)
-  // block groups of the MFMA pass (contiguous blocks): group g's strips are
-  // d_strips[gs[g] .. gs[g+1]), its panels d_spanels[gp[g] .. gp[g+1]) -- group
-  // g's finalize runs on the side stream while group g + 1's strips run
-  int ngrp = 1;
-  std::vector<int> gs, gp;
+  // MFMA pass: the 512-column strips of every packed block (class-1 items);
+  // a group's finalize runs on the side stream while the next group's strips run
+  StripSet s512;
+  // Wide strips (k_sym_mfma_wide, 1,024-column items) of the dense-triangle
+  // blocks, and the 512-column strips of the plan's other packed blocks (band
+  // blocks; empty when there are none): a pass that takes the wide form runs
+  // `wide`, then `rest` with its partials behind the wide ones.  Which form a
+  // block takes depends on the block and the pass's column count alone.
+  StripSet wide, rest;
+  bool wide_idle = true;       // k_sym_mfma_wide: idle waves leave at the start
   // band walks (band_walk.hip, 3-8 columns): when every packed block is a band
   // of extent <= WALK_RMAX panels; the walk panel / item tables in creation
   // order, the head panels' finalize table, head / carry slot counts

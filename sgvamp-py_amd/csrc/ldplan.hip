@@ -15,9 +15,12 @@ void free_plan(LdPlan& p){
     if (p.d_items[k]) (void)hipFree(p.d_items[k]);
     if (p.d_panels[k]) (void)hipFree(p.d_panels[k]);
   }
-  if (p.d_strips) (void)hipFree(p.d_strips);
-  if (p.d_sitems) (void)hipFree(p.d_sitems);
-  if (p.d_spanels) (void)hipFree(p.d_spanels);
+  for (StripSet* q : {&p.s512, &p.wide, &p.rest}) {
+    if (q->d_strips) (void)hipFree(q->d_strips);
+    if (q->d_sitems) (void)hipFree(q->d_sitems);
+    if (q->d_panels) (void)hipFree(q->d_panels);
+    if (q->d_wpanels) (void)hipFree(q->d_wpanels);
+  }
   if (p.d_ctasks) (void)hipFree(p.d_ctasks);
   if (p.d_walks) (void)hipFree(p.d_walks);
   if (p.d_wpanels) (void)hipFree(p.d_wpanels);
@@ -183,22 +186,44 @@ static int mfma_pair_choice(const std::vector<SymStrip>& strips,
 // The chunk's strips hold the column sums of panel G's rows (offset 0, "own")
 // and of panel G + 1's rows (offset 256, "other").  Dispatch order: by block
 // group (pass_groups), then most panels first (the short strips fill the tail).
+// wide: the same from the class-0 (1,024-column) tables -- chunks c0 = 256 p +
+// 1024 k, p = 0..3, panels g = p, p + 4, ..., G; a chunk's strips hold the
+// column sums of panels G .. G + 3 at row offsets 0 .. 768 (SymPanelW).
+// which: the blocks taken -- 0 every packed block, 1 the dense triangles (ext
+// = 0: the blocks the wide form runs), 2 the others.  The panel table holds
+// the taken blocks' panels only; a strip's shape depends on its block alone.
 static int build_strips(sgv_ctx* c, int ld, const std::vector<SymItem>& items,
-                        const std::vector<SymPanel>& panels, LdPlan* pl) {
-  constexpr int cw = 512;
+                        const std::vector<SymPanel>& panels, bool wide, int which,
+                        StripSet* out) {
+  const int cw = wide ? MFW_CW : 512;
   const int S = MFMA_STRIP;
-  constexpr int NPAR = cw / SYM_H;   // 512-column chunks start at 256 p + 512 k
+  const int NPAR = cw / SYM_H;       // chunks start at 256 p + cw k
+  auto taken = [&](int b) {
+    const LdBlock& lb = c->ldb[ld][b];
+    return lb.fmt == 1 && (which == 0 || (which == 1) == (lb.ext == 0));
+  };
   std::vector<SymItem> sitems;
   std::vector<SymStrip> strips;
   std::vector<int> sblk;             // block of each strip (creation order)
-  std::vector<SymPanel> sp = panels;
-  std::vector<int> pblk(panels.size(), 0);
+  std::vector<SymPanelW> sp;         // the taken blocks' panels
+  std::vector<int> pblk;
   int bp0 = 0;
   for (int b = 0; b < c->nblk; ++b) {
     if (c->ldb[ld][b].fmt != 1) continue;
     const int64_t n = c->bn[b];
     const int np = (int)c->ldb[ld][b].poff.size();
-    for (int g = 0; g < np; ++g) pblk[bp0 + g] = b;
+    if (!taken(b)) {
+      bp0 += np;
+      continue;
+    }
+    const int sp0 = (int)sp.size();
+    for (int g = 0; g < np; ++g) {
+      SymPanelW w;
+      w.p = panels[bp0 + g];
+      for (int k = 0; k < 4; ++k) w.sb[k] = w.se[k] = 0;
+      sp.push_back(w);
+      pblk.push_back(b);
+    }
     for (int p = 0; p < NPAR; ++p)
       for (int64_t c0 = (int64_t)SYM_H * p; c0 < n; c0 += cw) {
         const int G = (int)(c0 / SYM_H);
@@ -226,26 +251,30 @@ static int build_strips(sgv_ctx* c, int ld, const std::vector<SymItem>& items,
           strips.push_back(st);
           sblk.push_back(b);
         }
-        sp[bp0 + G].own_sb = sb;
-        sp[bp0 + G].own_se = (int)strips.size();
-        if (NPAR == 2 && G + 1 < np) {
-          sp[bp0 + G + 1].oth_sb = sb;
-          sp[bp0 + G + 1].oth_se = (int)strips.size();
-        }
+        for (int k = 0; k < NPAR; ++k)
+          if (G + k < np) {
+            sp[sp0 + G + k].sb[k] = sb;
+            sp[sp0 + G + k].se[k] = (int)strips.size();
+          }
       }
     bp0 += np;
   }
-  // block groups: contiguous blocks, balanced by stored bytes
+  *out = StripSet();
+  out->nslots_items = (int)items.size();
+  if (strips.empty()) return SGV_OK;
+  // block groups: contiguous blocks, balanced by stored bytes; the wide kernel
+  // holds a whole CU, the 4-wave kernel half of one
   const int ncu = device_cus();
   std::vector<int> grp(c->nblk, 0);
-  int ngrp = pass_groups((int)strips.size(), c->nblk, 2 * ncu);
+  int ngrp = pass_groups((int)strips.size(), c->nblk, wide ? ncu : 2 * ncu);
   {
+    auto bytes = [&](int b) { return which == 0 || taken(b) ? c->ldb[ld][b].stored_bytes : 0.0; };
     double tot = 0.0;
-    for (int b = 0; b < c->nblk; ++b) tot += c->ldb[ld][b].stored_bytes;
+    for (int b = 0; b < c->nblk; ++b) tot += bytes(b);
     double acc = 0.0;
     for (int b = 0; b < c->nblk; ++b) {
       grp[b] = std::min(ngrp - 1, (int)(acc / tot * ngrp));
-      acc += c->ldb[ld][b].stored_bytes;
+      acc += bytes(b);
     }
     ngrp = grp[c->nblk - 1] + 1;
   }
@@ -268,12 +297,12 @@ static int build_strips(sgv_ctx* c, int ld, const std::vector<SymItem>& items,
       return strips[x].npan > strips[y].npan;
     });
     std::vector<SymStrip> o(strips.size());
-    pl->gs.assign(ngrp + 1, 0);
+    out->gs.assign(ngrp + 1, 0);
     for (size_t i = 0; i < ord.size(); ++i) {
       o[i] = strips[ord[i]];
-      pl->gs[grp[sblk[ord[i]]] + 1] = (int)i + 1;
+      out->gs[grp[sblk[ord[i]]] + 1] = (int)i + 1;
     }
-    for (int g = 1; g <= ngrp; ++g) pl->gs[g] = std::max(pl->gs[g], pl->gs[g - 1]);
+    for (int g = 1; g <= ngrp; ++g) out->gs[g] = std::max(out->gs[g], out->gs[g - 1]);
     strips.swap(o);
   }
   // finalize dispatch order (a panel's sums do not depend on it): by group, then
@@ -282,32 +311,64 @@ static int build_strips(sgv_ctx* c, int ld, const std::vector<SymItem>& items,
   {
     std::vector<int> ord(sp.size());
     for (size_t i = 0; i < ord.size(); ++i) ord[i] = (int)i;
-    auto work = [&](const SymPanel& a) {
-      return (a.item_end - a.item_begin) + (a.own_se - a.own_sb) + (a.oth_se - a.oth_sb);
+    auto work = [&](const SymPanelW& a) {
+      int w = a.p.item_end - a.p.item_begin;
+      for (int k = 0; k < 4; ++k) w += a.se[k] - a.sb[k];
+      return w;
     };
     std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) {
       if (grp[pblk[x]] != grp[pblk[y]]) return grp[pblk[x]] < grp[pblk[y]];
       return work(sp[x]) > work(sp[y]);
     });
-    std::vector<SymPanel> o(sp.size());
-    pl->gp.assign(ngrp + 1, 0);
+    std::vector<SymPanelW> o(sp.size());
+    out->gp.assign(ngrp + 1, 0);
     for (size_t i = 0; i < ord.size(); ++i) {
       o[i] = sp[ord[i]];
-      pl->gp[grp[pblk[ord[i]]] + 1] = (int)i + 1;
+      out->gp[grp[pblk[ord[i]]] + 1] = (int)i + 1;
     }
-    for (int g = 1; g <= ngrp; ++g) pl->gp[g] = std::max(pl->gp[g], pl->gp[g - 1]);
+    for (int g = 1; g <= ngrp; ++g) out->gp[g] = std::max(out->gp[g], out->gp[g - 1]);
     sp.swap(o);
   }
-  pl->ngrp = ngrp;
-  pl->nstrips = (int)strips.size();
-  pl->ragged = false;
+  out->ngrp = ngrp;
+  out->nstrips = (int)strips.size();
+  out->nsitems = (int)sitems.size();
+  out->npanels = (int)sp.size();
+  out->ragged = false;
   for (const SymStrip& st : strips)
-    for (int i = 0; i < st.npan; ++i) pl->ragged |= sitems[st.it0 + i].nc < st.ncmax;
-  pl->pair = pl->ragged ? 0 : mfma_pair_choice(strips, sitems);
-  CHK(upload_table(c, strips, &pl->d_strips));
-  CHK(upload_table(c, sitems, &pl->d_sitems));
-  CHK(upload_table(c, sp, &pl->d_spanels));
+    for (int i = 0; i < st.npan; ++i) out->ragged |= sitems[st.it0 + i].nc < st.ncmax;
+  out->pair = (wide || out->ragged) ? 0 : mfma_pair_choice(strips, sitems);
+  CHK(upload_table(c, strips, &out->d_strips));
+  CHK(upload_table(c, sitems, &out->d_sitems));
+  if (wide) {
+    CHK(upload_table(c, sp, &out->d_wpanels));
+  } else {
+    std::vector<SymPanel> p512(sp.size());
+    for (size_t i = 0; i < sp.size(); ++i) {
+      p512[i] = sp[i].p;
+      p512[i].own_sb = sp[i].sb[0];
+      p512[i].own_se = sp[i].se[0];
+      p512[i].oth_sb = sp[i].sb[1];
+      p512[i].oth_se = sp[i].se[1];
+    }
+    CHK(upload_table(c, p512, &out->d_panels));
+  }
   return SGV_OK;
+}
+
+// Which passes take the wide strips on dense-triangle blocks: every 3-8-column
+// pass (one box, parent and this build alternating three times,
+// profiles/r07/ldpass_ab.jsonl: 64 x 15,625 at 4 columns -2.1 % per pass, the
+// 8-block share -1.5 %; the north star's bench line +2.3 % it/s).
+// SGV_MF_WIDE=0 / 1 (with SGV_AB=1): none / every 3-8-column pass; a forced
+// SGV_MF_PAIR keeps the 512-column forms it selects between.  A function of
+// the column count alone, read per pass (a getenv).
+static bool wide_pass(int nc) {
+  if (nc < 3 || nc > 8) return false;
+  const char* e = ab_env("SGV_MF_WIDE");
+  if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
+  const char* p = ab_env("SGV_MF_PAIR");
+  if (p && (p[0] == '0' || p[0] == '1')) return false;
+  return true;
 }
 
 // Band walks of LD matrix ld (band_walk.hip) from the class-1 tables in
@@ -597,8 +658,16 @@ int ensure_plan(sgv_ctx* c, int ld){
       CHK(upload_table(c, order, &pl.d_items[cls]));
     }
     CHK(upload_table(c, panels, &pl.d_panels[cls]));
+    if (cls == 0) {
+      CHK(build_strips(c, ld, items, panels, true, 1, &pl.wide));
+      // SGV_MF_WIDE_IDLE=0 (with SGV_AB=1): the idle waves of a ragged chunk stay
+      // and add zeros (the A/B of their exit)
+      const char* e = ab_env("SGV_MF_WIDE_IDLE");
+      pl.wide_idle = !(e && e[0] == '0');
+    }
     if (cls == 1) {
-      CHK(build_strips(c, ld, items, panels, &pl));
+      CHK(build_strips(c, ld, items, panels, false, 0, &pl.s512));
+      if (pl.wide.nstrips) CHK(build_strips(c, ld, items, panels, false, 2, &pl.rest));
       CHK(plan_walks(c, ld, items, panels, &pl));
     }
     const size_t ncmax = (size_t)sym_class_nc(cls);
@@ -607,7 +676,11 @@ int ensure_plan(sgv_ctx* c, int ld){
   }
   if (pl.npanels) {   // the MFMA pass: class-1 items with up to 16 columns
     rowpart_need = std::max(rowpart_need, (size_t)pl.nitems[1] * SYM_H * MAXC);
-    colpart_need = std::max(colpart_need, (size_t)pl.nstrips * MAXC * 512);
+    colpart_need = std::max(colpart_need, (size_t)pl.s512.nstrips * MAXC * 512);
+    // a wide pass (up to 8 columns): the wide items and slots, then the other
+    // blocks' 512-column ones behind them
+    rowpart_need = std::max(rowpart_need, ((size_t)pl.wide.nslots_items + (pl.rest.nstrips ? pl.rest.nslots_items : 0)) * SYM_H * 8);
+    colpart_need = std::max(colpart_need, ((size_t)pl.wide.nstrips * MFW_CW + (size_t)pl.rest.nstrips * 512) * 8);
     CHK(grow(c, &c->d_pk, &c->pk_cap, (size_t)c->Mpad * 16));
   }
   CHK(grow(c, &c->d_rowpart, &c->rowpart_cap, rowpart_need));
@@ -664,40 +737,71 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
     const int cls = mf ? 1 : sym_class(nc);
     if (mf) {
       const bool walk = pl.nwalks && nc <= band_walk_max_nc();
+      double mf_aux = 0.0;
       HIPCHK(launch_pk(pa, nc, c->Mpad, c->d_pk, c->st,
                        walk ? nc > 4 : strip_pk_paired(nc)));
       if (walk) {   // band plan: the walks, then the head panels
         HIPCHK(launch_band_walk(nc, pl.d_walks, pl.nwalks, pl.d_wpanels, pl.d_witems, c->d_pk,
                                 c->Mpad, pa,
                                 c->d_whead, c->d_wcarry, pl.d_wfins, pl.nwfins, c->d_part, c->st));
-      } else if (pl.ngrp <= 1) {
-        HIPCHK(launch_sym_mfma(nc, pl.d_strips, pl.nstrips, pl.d_sitems, pa, c->d_pk,
-                               c->d_rowpart, c->d_colpart, pl.ragged, pl.pair, c->st));
-        HIPCHK(launch_sym_finalize_strip(nc, pl.d_spanels, pl.npanels, pa, c->d_rowpart,
-                                         c->d_colpart, c->d_part, pl.ragged, c->st));
       } else {
-        // group g's strips on the ctx stream, its finalize on the side stream
-        // behind them: the finalize (and the launch tail) of g overlaps g + 1's
-        // strips.  Same work items, so the products are bitwise the one-launch
-        // pass's; the pass's events (e0 on st, e1 after the join) span both
-        for (int g = 0; g < pl.ngrp; ++g) {
-          HIPCHK(launch_sym_mfma(nc, pl.d_strips + pl.gs[g], pl.gs[g + 1] - pl.gs[g],
-                                 pl.d_sitems, pa, c->d_pk, c->d_rowpart, c->d_colpart, pl.ragged,
-                                 pl.pair, c->st));
-          HIPCHK(hipEventRecord(c->ev_grp[g % MAXGRP], c->st));
-          HIPCHK(hipStreamWaitEvent(c->st_fin, c->ev_grp[g % MAXGRP], 0));
-          HIPCHK(launch_sym_finalize_strip(nc, pl.d_spanels + pl.gp[g], pl.gp[g + 1] - pl.gp[g],
-                                           pa, c->d_rowpart, c->d_colpart, c->d_part, pl.ragged,
-                                           c->st_fin));
+        // One strip set: group g's strips on the ctx stream, its finalize on the
+        // side stream behind them, so the finalize (and the launch tail) of g
+        // overlaps g + 1's strips.  Same work items, so the products are bitwise
+        // the one-launch pass's; the pass's events (e0 on st, e1 after the join)
+        // span both.  rp / cp: the set's partials
+        const bool usew = pl.wide.nstrips > 0 && wide_pass(nc);
+        bool side = false;
+        auto run_set = [&](const StripSet& ss, bool wide, double* rp, double* cp) -> int {
+          for (int g = 0; g < ss.ngrp; ++g) {
+            const int s0 = ss.gs[g], ns = ss.gs[g + 1] - s0;
+            const int p0 = ss.gp[g], npn = ss.gp[g + 1] - p0;
+            const bool split = ss.ngrp > 1;
+            if (wide)
+              HIPCHK(launch_sym_mfma_wide(nc, ss.d_strips + s0, ns, ss.d_sitems, pa, c->d_pk, rp,
+                                          cp, pl.wide_idle, c->st));
+            else
+              HIPCHK(launch_sym_mfma(nc, ss.d_strips + s0, ns, ss.d_sitems, pa, c->d_pk, rp, cp,
+                                     ss.ragged, ss.pair, c->st));
+            hipStream_t fs = c->st;
+            if (split) {
+              HIPCHK(hipEventRecord(c->ev_grp[g % MAXGRP], c->st));
+              HIPCHK(hipStreamWaitEvent(c->st_fin, c->ev_grp[g % MAXGRP], 0));
+              fs = c->st_fin;
+              side = true;
+            }
+            if (wide)
+              HIPCHK(launch_sym_finalize_wide(nc, ss.d_wpanels + p0, npn, pa, rp, cp, c->d_part,
+                                              fs));
+            else
+              HIPCHK(launch_sym_finalize_strip(nc, ss.d_panels + p0, npn, pa, rp, cp, c->d_part,
+                                               ss.ragged, fs));
+          }
+          return SGV_OK;
+        };
+        if (usew) {
+          CHK(run_set(pl.wide, true, c->d_rowpart, c->d_colpart));
+          if (pl.rest.nstrips)
+            CHK(run_set(pl.rest, false, c->d_rowpart + (size_t)pl.wide.nslots_items * SYM_H * nc,
+                        c->d_colpart + (size_t)pl.wide.nstrips * MFW_CW * nc));
+          mf_aux = 2.0 * 8.0 * nc * ((double)pl.wide.nsitems * SYM_H +
+                                     (double)pl.wide.nstrips * MFW_CW +
+                                     (double)pl.rest.nsitems * SYM_H +
+                                     (double)pl.rest.nstrips * 512);
+        } else {
+          CHK(run_set(pl.s512, false, c->d_rowpart, c->d_colpart));
+          mf_aux = 2.0 * 8.0 * nc * ((double)pl.s512.nsitems * SYM_H +
+                                     (double)pl.s512.nstrips * 512);
         }
-        HIPCHK(hipEventRecord(c->ev_fin, c->st_fin));
-        HIPCHK(hipStreamWaitEvent(c->st, c->ev_fin, 0));
+        if (side) {
+          HIPCHK(hipEventRecord(c->ev_fin, c->st_fin));
+          HIPCHK(hipStreamWaitEvent(c->st, c->ev_fin, 0));
+        }
       }
       if (walk)   // head partials and carries, written and read
         c->aux_bytes += 2.0 * 8.0 * nc * SYM_H * (double)(pl.nhslots + pl.ncslots);
-      else
-        c->aux_bytes += 2.0 * 8.0 * nc * ((double)pl.nitems[cls] * SYM_H +
-                                          (double)pl.nstrips * 512);
+      else   // the row and column partials of the strips launched, written and read
+        c->aux_bytes += mf_aux;
       c->aux_bytes += 8.0 * (double)c->Mpad * ((nc <= 4 ? 4 : nc <= 8 ? 8 : 16) + nc);   // Pk pack
     } else {
       HIPCHK(launch_sym_pass(nc, cls, pl.d_items[cls], pl.nitems[cls], pa, c->d_rowpart,

@@ -476,8 +476,19 @@ extern "C" int sgv_em(sgv_ctx* c, const double* gam1s, const double* a, int nsla
     // one-rank loop over every rank's gathered r1.
     const bool rep = em_mode_pick(c, maxit);
     const bool fuse = rep || (!c->comm && !c->host_ag && fused_ctl_pays(EM_NV, c->nblk));
-    hipEvent_t em0, em1;   // the loop on the device: its r1 gather to its last step
+    hipEvent_t em0 = nullptr, em1 = nullptr;   // the loop on the device: its r1 gather to its last step
     CHK(event_pair(c, &em0, &em1));
+    // an error return below hands the pair back to the pool (until empending holds it)
+    struct PairBack {
+      sgv_ctx* c;
+      hipEvent_t *a, *b;
+      ~PairBack() {
+        if (*a) {
+          c->evpool.push_back(*a);
+          c->evpool.push_back(*b);
+        }
+      }
+    } pair_back{c, &em0, &em1};
     HIPCHK(hipEventRecord(em0, c->st));
     const ChunkDesc* ech = rep ? c->d_chg : c->d_ch;
     const int* ebeg = rep ? c->d_chg_begin : c->d_ch_begin;
@@ -518,6 +529,7 @@ extern "C" int sgv_em(sgv_ctx* c, const double* gam1s, const double* a, int nsla
     if (em0) {   // maxit reached without convergence: the loop ends with its last step
       HIPCHK(hipEventRecord(em1, c->st));
       c->empending.push_back({em0, em1});
+      em0 = em1 = nullptr;
     }
     *lam_io = last->lam;
     for (int l = 0; l < nslab; ++l) omegas_io[l] = last->om[l];

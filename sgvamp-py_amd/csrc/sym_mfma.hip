@@ -669,6 +669,272 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_pair(const SymStrip* __rest
   }
 }
 
+// Wide strips (dense-triangle blocks, 3-8 columns): one 8-wave workgroup per
+// strip of a 1,024-column chunk, one per CU; wave w owns chunk columns
+// [128 w, 128 w + 128) and runs k_sym_mfma's DEF path on them (the same
+// fragment loads, tile, operands, deferred row MFMAs and dummy loads).  An item
+// is a (panel, 1,024-column chunk) pair, so a pass writes and reads back half
+// the row partials of the 512-column forms.
+// Row sums: per 16-row group each wave reduces its 4 blocks (DPP), writes its
+// 16 x 4 NG sums into hand-off buffer gg mod MFW_RD and bumps the buffer's
+// arrival counter; wave gg mod nact adds the segments in wave order and writes
+// the group's 16 x ncol sums straight to rowpart (band_walk.hip's pattern:
+// wavefront-scope fences, workgroup-scope relaxed counters; a wave runs up to
+// MFW_RD - 1 row groups ahead of the slowest).  No barrier after the start.
+// idle: a wave whose whole segment lies past the strip's last column (the
+// ragged last chunk of a column class) would add exact zeros; it leaves at the
+// start and the combine counts the nact waves left.
+// Column sums: one chain per column over the strip's rows, as k_sym_mfma.
+// The summation order differs from the 512-column forms' (a row's item sums
+// are eight 128-column segments over 1,024 columns), so the bits do: which
+// form a block takes is a function of the block alone (ldplan.hip).
+constexpr int MFW_RD = 4;   // hand-off buffers (32 KiB at NG = 2, beside 32 KiB of tiles)
+template <int NG, int PD, bool PP = false>
+__global__ __launch_bounds__(512, 1) void k_sym_mfma_wide(const SymStrip* __restrict__ strips,
+                                                          const SymItem* __restrict__ sitems,
+                                                          const double* __restrict__ pk, int ncol,
+                                                          double* __restrict__ rowpart,
+                                                          double* __restrict__ colpart,
+                                                          const int* __restrict__ run, int idle) {
+  constexpr int NW = 8;
+  constexpr int WC = MFW_CW / NW;  // columns per wave
+  constexpr int NT = WC / 32;      // 32-column steps per wave
+  static_assert(PD >= 1 && PD <= NT && NT % PD == 0, "prefetch depth divides the steps");
+  constexpr int RW = 4 * NG;
+  constexpr bool SWZ = NG == 2;    // k_sym_mfma's row sets
+  __shared__ __attribute__((aligned(16))) double hand[MFW_RD][NW][16 * RW];
+  __shared__ int hready[MFW_RD], hdone[MFW_RD];   // writes into / combines of each buffer
+  __shared__ __attribute__((aligned(16))) double stg[NW][16 * 32];
+  const SymStrip sp = strips[blockIdx.x];
+  if (run && !ldg(run)) return;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int lo = lane & 15, hi = lane >> 4, bq = (lane >> 2) & 3, n4 = lane & 3;
+  const int pc = hi + 4 * bq;
+  SymItem cur = sitems[sp.it0];
+  const int c0 = cur.c0, ncc = sp.ncmax;
+  constexpr int PKS = 4 * NG;      // Pk row stride (k_pack)
+  const double* pkb = pk + (int64_t)cur.voff * PKS;
+  const int cw0 = wid * WC;
+  const bool dhalf = cw0 < SYM_H;                      // waves 0 and 1: the diagonal block
+  const int nta = min(NT, max(0, (ncc - cw0 + 31) / 32));
+  // waves with columns inside the strip
+  const int nact = idle ? min(NW, (ncc + WC - 1) / WC) : NW;
+  if (threadIdx.x < MFW_RD) hready[threadIdx.x] = hdone[threadIdx.x] = 0;
+  __syncthreads();
+  if (wid >= nact) return;
+  double* sb = stg[wid];
+  auto lds_wait_ge = [](int* ctr, int v) {
+    while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < v)
+      __builtin_amdgcn_s_sleep(1);
+  };
+
+  static_assert(!PP || NG == 2, "paired Pk rows: two column groups");
+  auto ld_prow = [&](int64_t row, double* v) {   // as k_sym_mfma's
+    if constexpr (PP) {
+      const d2 x = ldg((const d2*)(pkb + row * PKS + 2 * n4));
+      v[0] = x.x;
+      v[1] = x.y;
+    } else {
+#pragma unroll
+      for (int q = 0; q < NG; ++q) v[q] = ldg(pkb + row * PKS + 4 * q + n4);
+    }
+  };
+  double brow[NT][2][NG];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int col = cw0 + 32 * t + 2 * pc + e;
+      double v[NG];
+      ld_prow(c0 + (col < ncc ? col : 0), v);
+#pragma unroll
+      for (int q = 0; q < NG; ++q) brow[t][e][q] = col < ncc ? v[q] : 0.0;
+    }
+  double dcol[NT][2][NG];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int q = 0; q < NG; ++q) dcol[t][e][q] = 0.0;
+
+  auto load_cf = [&](uint64_t b0, int64_t ws, int H, int g, int t, d2* cf) {
+    asm volatile("" : "+s"(b0));
+    const int xc = cw0 + 32 * t + 2 * lo;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int rB = 16 * g + 4 * (SWZ ? a ^ (bq & 2) : a) + hi;
+      const double* row = (const double*)b0 + (int64_t)(rB < H ? rB : H - 1) * ws;
+      cf[a] = ldg_nt((const d2*)(row + (xc < ncc ? xc : 0)));
+    }
+  };
+  auto load_bcol = [&](int r0, int H, bool zero, int g, double (*bc)[NG]) {
+#pragma unroll
+    for (int a = 0; a < (SWZ ? 1 : 4); ++a) {
+      const int rB = 16 * g + 4 * (SWZ ? bq : a) + hi;
+      double v[NG];
+      ld_prow(r0 + (rB < H ? rB : 0), v);
+#pragma unroll
+      for (int q = 0; q < NG; ++q) bc[a][q] = (rB < H && !zero) ? v[q] : 0.0;
+    }
+  };
+  auto pbase = [&](const SymItem& x) { return (uint64_t)(x.P + (x.c0 - x.r0)); };
+
+  uint64_t curb = pbase(cur);
+  d2 cfq[PD][4];
+  double bcn[SWZ ? 1 : 4][NG];
+#pragma unroll
+  for (int p = 0; p < PD; ++p) load_cf(curb, cur.w, cur.H, 0, p, cfq[p]);
+  load_bcol(cur.r0, cur.H, dhalf && cur.r0 == c0, 0, bcn);
+
+  // this lane's place in the strip's colpart slot, kept in vector registers
+  // over the loops (the scalar file is full: no spills)
+  double* outp = colpart + ((int64_t)sp.slot * ncol + n4) * MFW_CW + cw0 + 2 * pc;
+  asm volatile("" : "+v"(outp));
+  int gg = 0;   // row groups done: buffer gg % MFW_RD, round gg / MFW_RD
+#pragma unroll 1
+  for (int s = 0; s < sp.npan; ++s) {                  // uniform over the workgroup
+    const bool more = s + 1 < sp.npan;
+    const SymItem nx = sitems[sp.it0 + (more ? s + 1 : s)];
+    const uint64_t nxb = more ? pbase(nx) : (uint64_t)pkb;
+    const int ng = (cur.H + 15) / 16;
+#pragma unroll 1
+    for (int g = 0; g < ng; ++g) {
+      const bool same = g + 1 < ng;
+      const uint64_t gb = same ? curb : nxb;
+      const int64_t gw = same ? cur.w : (more ? nx.w : 0);
+      const int gH = same ? cur.H : (more ? nx.H : 1);
+      const int gn = same ? g + 1 : 0;
+      const int gr0 = same ? cur.r0 : nx.r0;
+      const bool gz = dhalf && gr0 == c0;
+      double bcol[4][NG];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int q = 0; q < NG; ++q) bcol[a][q] = SWZ ? swz_quad(bcn[0][q], a) : bcn[SWZ ? 0 : a][q];
+      double drow[4][NG];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int q = 0; q < NG; ++q) drow[r][q] = 0.0;
+      const bool colz = dhalf && cur.r0 == c0;   // this panel's column B operands are 0
+      d2 rfb[2][4];                               // row fragments: this and the previous step
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        d2 cf[4];
+        d2* rf = rfb[t & 1];
+        const int slot = t % PD;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) cf[a] = cfq[slot][a];
+        if (t + PD < NT) {
+          load_cf(curb, cur.w, cur.H, g, t + PD, cfq[slot]);
+        } else {
+          load_cf(gb, gw, gH, gn, t + PD - NT, cfq[slot]);
+          if (t + PD == NT) load_bcol(gr0, gH, gz, gn, bcn);
+        }
+        if (t >= nta) continue;                        // wave-uniform: past the chunk
+        lds_order();
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+          *(d2*)(sb + 32 * (4 * (SWZ ? a ^ (bq & 2) : a) + hi) + 2 * (lo ^ hi)) = cf[a];
+        lds_order();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rf[r] = *(const d2*)(sb + 32 * (4 * r + n4) + 2 * (pc ^ n4));
+        __builtin_amdgcn_s_setprio(1);
+        // column level a of this step, then a quarter of the previous step's
+        // row MFMAs (k_sym_mfma's DEF order)
+        const d2* rp = rfb[(t + 1) & 1];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+          if (!colz) {
+#pragma unroll
+            for (int q = 0; q < NG; ++q) {
+              dcol[t][0][q] = MFMA4(cf[a].x, bcol[a][q], dcol[t][0][q]);
+              dcol[t][1][q] = MFMA4(cf[a].y, bcol[a][q], dcol[t][1][q]);
+            }
+          }
+          if (t > 0) {
+            const int tp = t > 0 ? t - 1 : 0;
+#pragma unroll
+            for (int r = 2 * (a & 1); r < 2 * (a & 1) + 2; ++r)
+#pragma unroll
+              for (int q = 0; q < NG; ++q)
+                drow[r][q] = MFMA4(a < 2 ? rp[r].x : rp[r].y, brow[tp][a < 2 ? 0 : 1][q], drow[r][q]);
+          }
+        }
+        if (t == NT - 1 || t + 1 == nta) {   // the row group's last active step: its own row MFMAs
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int q = 0; q < NG; ++q) drow[r][q] = MFMA4(rf[r].x, brow[t][0][q], drow[r][q]);
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int q = 0; q < NG; ++q) drow[r][q] = MFMA4(rf[r].y, brow[t][1][q], drow[r][q]);
+        }
+        __builtin_amdgcn_s_setprio(0);
+      }
+      // the row group's row sums: 4 blocks (DPP), handed to the combining wave
+      const int hs = gg % MFW_RD, gen = gg / MFW_RD;
+      lds_wait_ge(&hdone[hs], gen);                    // buffer hs free (its last round combined)
+      double* rb = hand[hs][wid];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int q = 0; q < NG; ++q) {
+          double v = drow[r][q];
+          v = v + row_ror<12>(v);
+          v = v + row_ror<8>(v);
+          if (bq == 0) rb[(4 * r + hi) * RW + 4 * q + n4] = v;   // D row 4r + m (m = hi)
+        }
+      // a wave's DS operations execute in order, so the counter's add lands
+      // after the row sums; the fences keep the compiler's order and wait for
+      // nothing (the fragments stay in flight)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      if (lane == 0)
+        __hip_atomic_fetch_add(&hready[hs], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      // the panel's row group g is combined by wave g mod 8 (wave 0 for an idle one)
+      if (wid == ((g & (NW - 1)) < nact ? (g & (NW - 1)) : 0)) {   // the waves in order
+        lds_wait_ge(&hready[hs], nact * (gen + 1));
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        double* dst = rowpart + ((int64_t)cur.item * SYM_H + 16 * g) * ncol;
+#pragma unroll
+        for (int k = 0; k < (16 * RW + WAVE - 1) / WAVE; ++k) {
+          const int e = lane + WAVE * k;
+          if (e < 16 * RW) {
+            const int row = e / RW, cc = e - row * RW;
+            const double* rr = &hand[hs][0][0] + e;
+            double v = rr[0];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) {   // branch-free: a wave that left adds 0
+              const double x = rr[w * 16 * RW];
+              v += w < nact ? x : 0.0;
+            }
+            if (16 * g + row < cur.H && cc < ncol) dst[row * ncol + cc] = v;
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        if (lane == 0)
+          __hip_atomic_store(&hdone[hs], gen + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      ++gg;
+    }
+    cur = nx;
+    curb = nxb;
+  }
+  // column sums over the strip's panels (whole 128-column segment, 16-B stores)
+#pragma unroll
+  for (int q = 0; q < NG; ++q) {
+    const int cc = 4 * q + n4;
+    if (cc < ncol) {
+      double* out = outp + 4 * q * MFW_CW;
+#pragma unroll
+      for (int t = 0; t < NT; ++t) *(d2*)(out + 32 * t) = d2{dcol[t][0][q], dcol[t][1][q]};
+    }
+  }
+}
+
 // 13..16 right-hand sides: v_mfma_f64_16x16x4f64 (one 16-column group, 140
 // cycles per 16x16x4) keeps fewer accumulators and B operands in registers
 // than four 4x4x4 groups, which spill at 4 waves.  Same strips as above:
@@ -961,6 +1227,42 @@ __global__ __launch_bounds__(256) void k_sym_finalize_strip1(
   if (t < NC) partials[(int64_t)pn.part * NC + t] = ((s_w[0][t] + s_w[1][t]) + s_w[2][t]) + s_w[3][t];
 }
 
+// k_sym_finalize_strip over the wide tables: part q sums the panel's
+// 1,024-column items item_begin + q, + FIN_Q, ..., then for k = 0..3 the strips
+// sb[k] + q, + FIN_Q, ... of the chunk starting k panels before this one (row
+// offset 256 k); parts added in order (fin_epilogue) -- fixed order throughout
+template <int NC>
+__global__ __launch_bounds__(256 * FIN_Q) void k_sym_finalize_wide(
+    const SymPanelW* __restrict__ panels, PassArgs pa, const double* __restrict__ rowpart,
+    const double* __restrict__ colpart, double* __restrict__ partials) {
+  const SymPanelW pw = panels[blockIdx.x];
+  const SymPanel& pn = pw.p;
+  if (pa.run && !ldg(pa.run)) return;
+  FinPre<NC> pre;
+  fin_prefetch<NC>(pn, pa, pre);
+  const int t = threadIdx.x & 255, q = threadIdx.x >> 8;
+  const int tr = t < pn.H ? t : 0;
+  double y[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) y[c] = 0.0;
+#pragma unroll 4
+  for (int itm = pn.item_begin + q; itm < pn.item_end; itm += FIN_Q) {
+    const double* rp = rowpart + ((int64_t)itm * SYM_H + t) * NC;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) y[c] += ldg(rp + c);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+#pragma unroll 4
+    for (int sl = pw.sb[k] + q; sl < pw.se[k]; sl += FIN_Q) {
+      const double* cp = colpart + (int64_t)sl * NC * MFW_CW + SYM_H * k + tr;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) y[c] += ldg(cp + c * MFW_CW);
+    }
+  }
+  fin_epilogue<NC>(pn, pa, y, partials, pre);
+}
+
 // Pk[i][c] = in[c][i] for c < ncol, 0 for ncol <= c < PKS (i over the padded
 // vector).  PKS = the columns the pass kernel's groups read: 4 (NC <= 4), 8
 // (NC <= 8), 16 -- a row is one cache line's worth of what is read, so the
@@ -1074,6 +1376,37 @@ hipError_t launch_sym_mfma(int nc, const SymStrip* d_strips, int nstrips, const 
                            d_sitems, d_pk, nc, rowpart, colpart, pa.run);
       break;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_sym_mfma_wide(int nc, const SymStrip* d_strips, int nstrips,
+                                const SymItem* d_sitems, const PassArgs& pa, const double* d_pk,
+                                double* rowpart, double* colpart, bool idle_exit, hipStream_t st) {
+  if (nc < 3 || nc > 8) return hipErrorInvalidValue;
+  if (nstrips <= 0) return hipSuccess;
+  if (nc <= 4)
+    hipLaunchKernelGGL((k_sym_mfma_wide<1, 2>), dim3(nstrips), dim3(512), 0, st, d_strips,
+                       d_sitems, d_pk, nc, rowpart, colpart, pa.run, idle_exit ? 1 : 0);
+  else   // Pk paired (strip_pk_paired)
+    hipLaunchKernelGGL((k_sym_mfma_wide<2, 2, true>), dim3(nstrips), dim3(512), 0, st, d_strips,
+                       d_sitems, d_pk, nc, rowpart, colpart, pa.run, idle_exit ? 1 : 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_sym_finalize_wide(int nc, const SymPanelW* d_panels, int npanels,
+                                    const PassArgs& pa, const double* rowpart,
+                                    const double* colpart, double* partials, hipStream_t st) {
+  if (npanels <= 0) return hipSuccess;
+#define FINW_CASE(N)                                                                         \
+  case N:                                                                                    \
+    hipLaunchKernelGGL(k_sym_finalize_wide<N>, dim3(npanels), dim3(256 * FIN_Q), 0, st,      \
+                       d_panels, pa, rowpart, colpart, partials);                            \
+    break;
+  switch (nc) {
+    FINW_CASE(3) FINW_CASE(4) FINW_CASE(5) FINW_CASE(6) FINW_CASE(7) FINW_CASE(8)
+    default: return hipErrorInvalidValue;
+  }
+#undef FINW_CASE
   return hipGetLastError();
 }
 
