@@ -161,8 +161,39 @@ int sgv_set_cg_exact(sgv_ctx* ctx, int mode);
 int sgv_set_ld_packing(sgv_ctx* ctx, int mode);
 /* fmt_out: 0 dense, 1 packed symmetric (triangle), 2 packed band, -1 not set. */
 int sgv_ld_block_format(sgv_ctx* ctx, int ld, int blk_local, int* fmt_out);
+/* Element type of PACKED blocks (triangle or band: symmetric blocks through
+ * sgv_set_ld_block with packing on, every sgv_set_ld_block_csr block, the
+ * blocks of sgv_synth_ld_g) set or generated from now on: bits = 64 (default)
+ * or 32; anything else is SGV_ERR_ARG.  With 32 every stored element is rounded
+ * ONCE, on store, to the nearest float (round to nearest even: numpy's
+ * astype(float32)) -- the host upload, the CSR panel assembly (after summing
+ * duplicates in f64) and the generator's store of G G^T (computed in f64) --
+ * in the same panels, stored extent and row stride (a multiple of 128
+ * elements) as the f64 layout, at 4 bytes per element.  Every product,
+ * accumulation, CG scalar and denoiser stays f64: the pass widens each element
+ * to f64 in registers and runs the same f64 MFMA chains, so a run is the exact
+ * f64 solve of a problem whose R was perturbed by <= 2^-24 relative per entry.
+ * A finite entry outside float's range fails the upload with SGV_ERR_ARG (the
+ * block is then unset); correlations never do.  A block stored as the full
+ * square (packing off, or not symmetric) stays f64 whatever the setting, and so
+ * do coupling matrices (sgv_set_ld_coupling).  All packed blocks of ONE LD
+ * matrix must share one precision (the first pass over a mixed matrix fails
+ * with SGV_ERR_STATE, naming the matrix); different LD matrices of a context may
+ * differ.  An f32 matrix runs every column count 1-16 on the 512-column MFMA
+ * strips, whatever sgv_set_mfma_min says (the VALU pass, the wave-pair and wide
+ * forms and the band walks are f64-only); a block's sums are a function of the
+ * block alone, within 1e-12 of the f64 product of the stored values (with
+ * SGV_AB=1 SGV_F32_FORM=1, the 8-byte load form, bitwise the f64 strips').
+ * Measured per pass against f64: 0.53-0.57x at 2-4 columns, 0.67-0.74x at 8,
+ * 0.83-0.88x at 16.  Bytes: sgv_ld_stored_bytes and
+ * sgv_timers t[2] count 4 bytes per stored element of an f32 block (the bytes
+ * actually stored); t[4], the dense-equivalent bytes, stays n^2 * 8. */
+int sgv_set_ld_precision(sgv_ctx* ctx, int bits);
+/* bits_out: 64 or 32, the element type block blk_local is stored in; -1 not set. */
+int sgv_ld_block_precision(sgv_ctx* ctx, int ld, int blk_local, int* bits_out);
 /* Bytes one pass over LD matrix ld reads from this rank's blocks that are set
- * (dense n^2*8, packed triangle / band: the stored panels).  Python's Engine
+ * (dense n^2*8, packed triangle / band: the stored panels, 8 or 4 bytes per
+ * element).  Python's Engine
  * sums it over ranks to pick the run's CG column-set mode (sgv_set_cg_exact). */
 int sgv_ld_stored_bytes(sgv_ctx* ctx, int ld, double* bytes_out);
 /* Coupling between consecutive band pieces gb and gb + 1 (global block
@@ -176,7 +207,8 @@ int sgv_ld_stored_bytes(sgv_ctx* ctx, int ld, double* bytes_out);
  * NULL where the rank owns neither piece): the exchange is collective.  Pieces
  * must be stored packed (sgv_set_ld_block_csr). */
 int sgv_set_ld_coupling(sgv_ctx* ctx, int ld, int gb, int nr, int nc, const double* C);
-/* Download one LD block (row-major n x n into a host array of row stride ld_host). */
+/* Download one LD block (row-major n x n into a host array of row stride
+ * ld_host): exactly the stored values, symmetric (an f32 block's widened). */
 int sgv_get_ld_block(sgv_ctx* ctx, int ld, int blk_local, double* rowmajor, int64_t ld_host);
 /* Start a new VAMP.infer on this context (src/sgvamp.py:198-217 restarts from
  * r1 = r, xhat2 = 0, Sigma2_u_prev = 0 on every call): zeroes every solver
@@ -373,7 +405,8 @@ int sgv_cg_solve(sgv_ctx* ctx, int ld, int ncol, const double* c1, const double*
 /* ---- timing -------------------------------------------------------------- */
 /* Summed over LD passes since the last reset (HIP events on the ctx stream):
  * t[0] = kernel time (ms), t[1] = passes, t[2] = LD bytes read (the stored
- * bytes: n^2*8 dense, sum over panels H*(n - r0)*8 packed), t[3] = RHS bytes
+ * bytes: n^2*8 dense, sum over panels H*(n - r0)*8 packed, * 4 for a block
+ * stored as f32: sgv_set_ld_precision), t[3] = RHS bytes
  * (2 * ncol * M_local * 8), t[4] = dense-equivalent LD bytes (n^2*8),
  * t[5] = packed-pass partial-buffer bytes (written + read), t[6] = the passes'
  * algorithmic flops (2 per multiply-add: each column's row part over every

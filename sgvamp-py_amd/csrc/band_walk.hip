@@ -170,7 +170,7 @@ __global__ __launch_bounds__(WK_NW * 64, 1) void k_band_walk(
   auto make = [&](const SymItem& it, const SymPanel& p) {
     Cur u;
     const int crel = it.c0 - it.r0;
-    u.b0 = it.P + crel;
+    u.b0 = (const double*)it.P + crel;
     u.w = (int)it.w;
     u.nc = it.nc;
     u.c0 = it.c0;

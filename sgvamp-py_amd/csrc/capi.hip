@@ -637,7 +637,7 @@ extern "C" int sgv_synth_ld_g(sgv_ctx* c, int ld, uint64_t seed, int64_t marker0
       const LdBlock& lb = c->ldb[ld][b];
       HIPCHK(launch_geno_G(seed, gm0, n, Nsamp, ldg, sb.mean, sb.sd, sb.G, c->st));
       HIPCHK(launch_syrk_nt(sb.G, n, Nsamp, ldg, lb.ptr, c->lda[b], lb.fmt, lb.d_poff, lb.d_pw,
-                            c->st));
+                            lb.bits, c->st));
     }
     HIPCHK(launch_g_accum(seed, gm0, n, Nsamp, sb.mean, sb.sd, sb.vec + c->boff[b], sb.g, c->st));
     CHK(ensure_hstage(c, sizeof(double) * Nsamp));

@@ -104,8 +104,9 @@ constexpr int SYM_H = 256;   // rows per panel
 constexpr int BAND_Q = 256;
 // one (panel, column chunk) work item of k_sym_pass
 struct SymItem {
-  const double* P;   // panel base: element (r0, r0)
-  int64_t w;         // panel row stride (doubles)
+  const void* P;     // panel base: element (r0, r0); double, or float for a block stored as
+                     // f32 (one type per table: LdPlan::bits; only the strip kernels read float)
+  int64_t w;         // panel row stride (elements of the stored type)
   int64_t voff;      // block's offset in the padded vector layout
   int32_t r0, H;     // panel first row (block-relative), rows
   int32_t c0, nc;    // chunk first column (block-relative), columns
@@ -167,8 +168,9 @@ struct WalkFin {
 };
 
 // element (i, j) of a packed block is stored iff j >= 256 * floor(i / 256)
-__device__ __forceinline__ double* sym_addr(double* base, const int64_t* poff, const int64_t* pw,
-                                            int i, int j) {
+template <class T>
+__device__ __forceinline__ T* sym_addr(T* base, const int64_t* poff, const int64_t* pw, int i,
+                                       int j) {
   const int g = i / SYM_H;
   const int r0 = g * SYM_H;
   if (j < r0) return nullptr;
@@ -390,7 +392,7 @@ hipError_t launch_pk(const PassArgs& pa, int nc, int64_t mpad, double* d_pk, hip
 bool strip_pk_paired(int nc);
 hipError_t launch_sym_mfma(int nc, const SymStrip* d_strips, int nstrips, const SymItem* d_sitems,
                            const PassArgs& pa, const double* d_pk, double* rowpart,
-                           double* colpart, bool ragged, int pair, hipStream_t st);
+                           double* colpart, bool ragged, int pair, int bits, hipStream_t st);
 // wide strips (3-8 columns, dense-triangle blocks): rowpart per (panel,
 // 1,024-column chunk) item, colpart slots 1,024 wide; idle_exit: waves wholly
 // past a strip's last column leave at once
@@ -674,9 +676,11 @@ hipError_t launch_geno_stats(uint64_t seed, int64_t gmarker0, int n, int nsamp, 
 hipError_t launch_geno_G(uint64_t seed, int64_t gmarker0, int n, int nsamp, int ldg,
                          const double* d_mean, const double* d_std, double* d_G,
                          hipStream_t st);
-// R = G G^T; packed != 0: write the packed symmetric layout (poff/pw per panel)
-hipError_t launch_syrk_nt(const double* d_G, int n, int nsamp, int ldg, double* d_R, int64_t lda,
-                          int packed, const int64_t* d_poff, const int64_t* d_pw, hipStream_t st);
+// R = G G^T; packed != 0: write the packed symmetric layout (poff/pw per panel);
+// bits = 32 (packed only): d_R holds floats, each f64 sum rounded on store
+hipError_t launch_syrk_nt(const double* d_G, int n, int nsamp, int ldg, void* d_R, int64_t lda,
+                          int packed, const int64_t* d_poff, const int64_t* d_pw, int bits,
+                          hipStream_t st);
 hipError_t launch_g_accum(uint64_t seed, int64_t gmarker0, int n, int nsamp, const double* d_mean,
                           const double* d_std, const double* d_beta, double* d_g, hipStream_t st);
 hipError_t launch_row_dot(const double* d_G, int n, int nsamp, int ldg, const double* d_y,

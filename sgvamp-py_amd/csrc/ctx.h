@@ -32,15 +32,21 @@
 using namespace sgv;
 // one LD block of one LD matrix
 struct LdBlock {
-  double* ptr = nullptr;
+  double* ptr = nullptr;       // the allocation; a packed block with bits = 32 holds floats (f32())
   int fmt = 0;                 // 0: dense n x lda row-major; 1: packed symmetric panels
+  int bits = 64;               // stored element type: 64, or 32 (packed blocks only,
+                               // sgv_set_ld_precision): same panels and strides, in elements
+  float* f32() const { return reinterpret_cast<float*>(ptr); }
+  size_t esz() const { return bits == 32 ? sizeof(float) : sizeof(double); }
   // packed band: panel g stores columns r0 .. r0 + min(n - r0, ext) - 1 only
   // (ext a multiple of BAND_Q; 0 = the whole upper triangle)
   int64_t ext = 0;
-  std::vector<int64_t> poff, pw;   // packed: panel offsets and row strides (doubles)
+  std::vector<int64_t> poff, pw;   // packed: panel offsets and row strides (elements)
   int64_t* d_poff = nullptr;
   int64_t* d_pw = nullptr;
   double stored_bytes = 0.0;   // bytes a pass reads: n^2*8 dense, sum H_g (n - r0_g)*8 packed
+                               // (* 4 at bits = 32): stored_elems * esz()
+  double stored_elems = 0.0;   // elements a pass reads
 };
 
 // coupling between consecutive band pieces gb and gb + 1 of one LD matrix (a
@@ -74,6 +80,8 @@ struct StripSet {
 
 struct LdPlan {
   bool valid = false;
+  int bits = 64;               // element type of every packed block (one per LD matrix: the
+                               // strip tables are single-typed); 32: every pass on s512
   RowGroup* d_rg = nullptr;    // dense blocks
   int nrg = 0;
   int* d_pbeg = nullptr;       // partial slots of block b: [pbeg[b], pbeg[b+1])
@@ -185,6 +193,7 @@ struct sgv_ctx {
   double* h_halo = nullptr;      // pinned staging of the host exchange (same layout)
   size_t h_halo_cap = 0;
   int packing = 1;               // 1: packed symmetric storage for symmetric blocks
+  int ld_bits = 64;              // element type of packed blocks set from now on (64 / 32)
   // MFMA passes in block groups (LdPlan::ngrp): the finalize of each group on
   // st_fin behind its strips' event, joined back into st at the pass end
   hipStream_t st_fin = nullptr;

@@ -42,20 +42,24 @@ static int64_t panel_ext(int64_t n, int64_t r0, int64_t ext) {
 }
 
 // allocate block b of LD matrix ld in format fmt (zero filled); ext: packed
-// band extent (0 = full upper triangle)
+// band extent (0 = full upper triangle).  A packed block takes the context's
+// element type (sgv_set_ld_precision); the full square is always f64
 int ld_alloc(sgv_ctx* c, int ld, int b, int fmt, int64_t ext){
   LdBlock& lb = c->ldb[ld][b];
   if (fmt == 0) ext = 0;
-  if (lb.ptr && lb.fmt == fmt && lb.ext == ext) return SGV_OK;
+  const int bits = fmt == 1 ? c->ld_bits : 64;
+  if (lb.ptr && lb.fmt == fmt && lb.ext == ext && lb.bits == bits) return SGV_OK;
   free_block(lb);
   c->plan[ld].valid = false;
   const int64_t n = c->bn[b];
   size_t elems = 0;
   lb.fmt = fmt;
   lb.ext = ext;
+  lb.bits = bits;
   if (fmt == 0) {
     elems = (size_t)c->lda[b] * (size_t)n;
-    lb.stored_bytes = (double)n * (double)n * 8.0;
+    lb.stored_elems = (double)n * (double)n;
+    lb.stored_bytes = lb.stored_elems * 8.0;
   } else {
     double valid = 0.0;
     for (int64_t r0 = 0; r0 < n; r0 += SYM_H) {
@@ -67,7 +71,8 @@ int ld_alloc(sgv_ctx* c, int ld, int b, int fmt, int64_t ext){
       elems += (size_t)(H * w);
       valid += (double)H * (double)e;
     }
-    lb.stored_bytes = valid * 8.0;
+    lb.stored_elems = valid;
+    lb.stored_bytes = valid * (double)lb.esz();
     HIPCHK(hipMalloc(&lb.d_poff, sizeof(int64_t) * lb.poff.size()));
     HIPCHK(hipMalloc(&lb.d_pw, sizeof(int64_t) * lb.pw.size()));
     HIPCHK(hipMemcpy(lb.d_poff, lb.poff.data(), sizeof(int64_t) * lb.poff.size(),
@@ -75,20 +80,21 @@ int ld_alloc(sgv_ctx* c, int ld, int b, int fmt, int64_t ext){
     HIPCHK(hipMemcpy(lb.d_pw, lb.pw.data(), sizeof(int64_t) * lb.pw.size(), hipMemcpyHostToDevice));
   }
   {
-    const hipError_t e = hipMalloc(&lb.ptr, sizeof(double) * elems);
+    const hipError_t e = hipMalloc(&lb.ptr, lb.esz() * elems);
     if (e != hipSuccess) {
       lb.ptr = nullptr;
       size_t fr = 0, tot = 0;
       (void)hipGetLastError();
       (void)hipMemGetInfo(&fr, &tot);
       return fail(c, SGV_ERR_HIP,
-                  "LD matrix %d block %d (n=%lld, %s): %.2f GB of device memory needed, %.2f GB "
-                  "free: %s", ld, b, (long long)n,
+                  "LD matrix %d block %d (n=%lld, %s, %s): %.2f GB of device memory needed, "
+                  "%.2f GB free: %s", ld, b, (long long)n,
                   fmt == 0 ? "dense" : ext > 0 ? "packed band" : "packed triangle",
-                  sizeof(double) * (double)elems / 1e9, (double)fr / 1e9, hipGetErrorString(e));
+                  bits == 32 ? "f32" : "f64", (double)lb.esz() * (double)elems / 1e9, (double)fr / 1e9,
+                  hipGetErrorString(e));
     }
   }
-  HIPCHK(hipMemsetAsync(lb.ptr, 0, sizeof(double) * elems, c->st));
+  HIPCHK(hipMemsetAsync(lb.ptr, 0, lb.esz() * elems, c->st));
   BlkDesc d{fmt == 0 ? lb.ptr : nullptr, c->lda[b], c->bn[b], c->bvoff[b]};
   HIPCHK(hipMemcpyAsync(c->d_blks[ld] + b, &d, sizeof d, hipMemcpyHostToDevice, c->st));
   CHK(stream_wait(c));
@@ -571,6 +577,21 @@ int ensure_plan(sgv_ctx* c, int ld){
   if (pl.valid) return SGV_OK;
   CHK(ld_ready(c, ld));
   free_plan(pl);
+  {   // one element type over the matrix's packed blocks: the strip tables are single-typed
+    int first = -1;
+    for (int b = 0; b < c->nblk; ++b) {
+      const LdBlock& lb = c->ldb[ld][b];
+      if (lb.fmt != 1) continue;
+      if (first < 0) first = b;
+      if (lb.bits != c->ldb[ld][first].bits)
+        return fail(c, SGV_ERR_STATE,
+                    "LD matrix %d: packed blocks of mixed precision (block %d is f%d, block %d "
+                    "f%d): set every block of one LD matrix under one sgv_set_ld_precision",
+                    ld, first, c->ldb[ld][first].bits, b, lb.bits);
+    }
+    pl.bits = first >= 0 ? c->ldb[ld][first].bits : 64;
+  }
+  const bool f32 = pl.bits == 32;   // every pass on the 512-column strips (ld_pass)
   std::vector<RowGroup> rg;
   std::vector<int> pbeg(c->nblk + 1, 0);
   const int rows = ld_pass_rows_per_group();
@@ -580,14 +601,14 @@ int ensure_plan(sgv_ctx* c, int ld){
     pbeg[b] = nparts;
     pl.stored_bytes += lb.stored_bytes;
     pl.dense_bytes += (double)c->bn[b] * (double)c->bn[b] * 8.0;
-    pl.mac_elems += lb.stored_bytes / 8.0;
+    pl.mac_elems += lb.stored_elems;
     if (lb.fmt == 1) {   // + the stored elements right of each panel's H x H diagonal block
       double diag = 0.0;
       for (int64_t r0 = 0; r0 < c->bn[b]; r0 += SYM_H) {
         const double H = (double)std::min<int64_t>(SYM_H, c->bn[b] - r0);
         diag += H * H;
       }
-      pl.mac_elems += lb.stored_bytes / 8.0 - diag;
+      pl.mac_elems += lb.stored_elems - diag;
     }
     if (lb.fmt == 0) {
       for (int64_t r0 = 0; r0 < c->bn[b]; r0 += rows) rg.push_back(RowGroup{b, (int32_t)r0, nparts++, 0});
@@ -619,7 +640,7 @@ int ensure_plan(sgv_ctx* c, int ld){
         const int64_t cend = r0 + panel_ext(n, r0, lb.ext);
         for (int64_t c0 = r0; c0 < cend; c0 += cw) {
           SymItem it;
-          it.P = lb.ptr + lb.poff[g];
+          it.P = f32 ? (const void*)(lb.f32() + lb.poff[g]) : (const void*)(lb.ptr + lb.poff[g]);
           it.w = lb.pw[g];
           it.voff = c->bvoff[b];
           it.r0 = r0;
@@ -658,7 +679,7 @@ int ensure_plan(sgv_ctx* c, int ld){
       CHK(upload_table(c, order, &pl.d_items[cls]));
     }
     CHK(upload_table(c, panels, &pl.d_panels[cls]));
-    if (cls == 0) {
+    if (cls == 0 && !f32) {
       CHK(build_strips(c, ld, items, panels, true, 1, &pl.wide));
       // SGV_MF_WIDE_IDLE=0 (with SGV_AB=1): the idle waves of a ragged chunk stay
       // and add zeros (the A/B of their exit)
@@ -668,7 +689,7 @@ int ensure_plan(sgv_ctx* c, int ld){
     if (cls == 1) {
       CHK(build_strips(c, ld, items, panels, false, 0, &pl.s512));
       if (pl.wide.nstrips) CHK(build_strips(c, ld, items, panels, false, 2, &pl.rest));
-      CHK(plan_walks(c, ld, items, panels, &pl));
+      if (!f32) CHK(plan_walks(c, ld, items, panels, &pl));
     }
     const size_t ncmax = (size_t)sym_class_nc(cls);
     rowpart_need = std::max(rowpart_need, items.size() * SYM_H * ncmax);
@@ -733,10 +754,13 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
   if (pl.halo || pl.nctasks) CHK(coupling_pass(c, pl, nc, pa));
   if (pl.nrg) HIPCHK(launch_ld_pass(nc, c->d_blks[ld], pl.d_rg, pl.nrg, pa, c->d_part, c->st));
   if (pl.npanels) {
-    const bool mf = c->mfma_min > 0 && nc >= c->mfma_min;
+    // an f32 matrix: every column count on the 512-column strips, the only
+    // kernels with float instances (its plan holds no wide strips or walks)
+    const bool f32 = pl.bits == 32;
+    const bool mf = f32 || (c->mfma_min > 0 && nc >= c->mfma_min);
     const int cls = mf ? 1 : sym_class(nc);
     if (mf) {
-      const bool walk = pl.nwalks && nc <= band_walk_max_nc();
+      const bool walk = !f32 && pl.nwalks && nc <= band_walk_max_nc();
       double mf_aux = 0.0;
       HIPCHK(launch_pk(pa, nc, c->Mpad, c->d_pk, c->st,
                        walk ? nc > 4 : strip_pk_paired(nc)));
@@ -750,7 +774,7 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
         // overlaps g + 1's strips.  Same work items, so the products are bitwise
         // the one-launch pass's; the pass's events (e0 on st, e1 after the join)
         // span both.  rp / cp: the set's partials
-        const bool usew = pl.wide.nstrips > 0 && wide_pass(nc);
+        const bool usew = !f32 && pl.wide.nstrips > 0 && wide_pass(nc);
         bool side = false;
         auto run_set = [&](const StripSet& ss, bool wide, double* rp, double* cp) -> int {
           for (int g = 0; g < ss.ngrp; ++g) {
@@ -762,7 +786,7 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
                                           cp, pl.wide_idle, c->st));
             else
               HIPCHK(launch_sym_mfma(nc, ss.d_strips + s0, ns, ss.d_sitems, pa, c->d_pk, rp, cp,
-                                     ss.ragged, ss.pair, c->st));
+                                     ss.ragged, f32 ? 0 : ss.pair, pl.bits, c->st));
             hipStream_t fs = c->st;
             if (split) {
               HIPCHK(hipEventRecord(c->ev_grp[g % MAXGRP], c->st));
@@ -814,7 +838,8 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
   }
   HIPCHK(hipEventRecord(e1, c->st));
   c->pending.emplace_back(e0, e1);
-  const bool wide = nc > 8 && pl.npanels && c->mfma_min > 0 && nc >= c->mfma_min;
+  const bool wide = nc > 8 && pl.npanels &&
+                    (pl.bits == 32 || (c->mfma_min > 0 && nc >= c->mfma_min));
   c->pending_wide.push_back(wide ? 1 : 0);
   c->ld_flops += 2.0 * nc * pl.mac_elems;
   if (wide) {
@@ -842,6 +867,35 @@ static bool host_symmetric(const double* A, int64_t n, int64_t ld) {
   return true;
 }
 
+// dst[i] = (float)src[i], round to nearest even (the host's default rounding
+// mode: numpy's astype(float32)); false when a finite value leaves float's range
+static bool narrow_f32(const double* src, float* dst, int64_t n) {
+  bool ok = true;
+  for (int64_t i = 0; i < n; ++i) {
+    const float f = (float)src[i];
+    ok &= !(std::isinf(f) && std::isfinite(src[i]));
+    dst[i] = f;
+  }
+  return ok;
+}
+
+extern "C" int sgv_set_ld_precision(sgv_ctx* c, int bits) {
+  ENTER(c);
+  if (bits != 64 && bits != 32)
+    return fail(c, SGV_ERR_ARG, "sgv_set_ld_precision: %d bits (64 or 32)", bits);
+  c->ld_bits = bits;
+  return SGV_OK;
+}
+
+extern "C" int sgv_ld_block_precision(sgv_ctx* c, int ld, int b, int* bits_out) {
+  ENTER(c);
+  if (ld < 0 || ld >= c->nld || b < 0 || b >= c->nblk || !bits_out)
+    return fail(c, SGV_ERR_ARG, "sgv_ld_block_precision: bad arguments");
+  const LdBlock& lb = c->ldb[ld][b];
+  *bits_out = lb.ptr ? lb.bits : -1;
+  return SGV_OK;
+}
+
 extern "C" int sgv_set_ld_packing(sgv_ctx* c, int mode) {
   ENTER(c);
   if (mode != 0 && mode != 1) return fail(c, SGV_ERR_ARG, "packing mode %d", mode);
@@ -856,10 +910,27 @@ extern "C" int sgv_set_ld_block(sgv_ctx* c, int ld, int b, const double* host, i
   const int64_t n = c->bn[b];
   const int fmt = (c->packing && host_symmetric(host, n, ld_host)) ? 1 : 0;
   CHK(ld_alloc(c, ld, b, fmt));
-  const LdBlock& lb = c->ldb[ld][b];
+  LdBlock& lb = c->ldb[ld][b];
   if (fmt == 0) {
     HIPCHK(hipMemcpy2D(lb.ptr, sizeof(double) * c->lda[b], host, sizeof(double) * ld_host,
                        sizeof(double) * n, n, hipMemcpyHostToDevice));
+  } else if (lb.bits == 32) {   // each panel's stored rows narrowed in pinned memory
+    CHK(ensure_hstage(c, sizeof(float) * (size_t)SYM_H * (size_t)n));
+    float* hp = (float*)c->h_stage;
+    for (size_t g = 0; g < lb.poff.size(); ++g) {
+      const int64_t r0 = (int64_t)g * SYM_H, H = std::min<int64_t>(SYM_H, n - r0), e = n - r0;
+      bool ok = true;
+      for (int64_t i = 0; i < H; ++i) ok &= narrow_f32(host + (r0 + i) * ld_host + r0, hp + i * e, e);
+      if (!ok) {
+        free_block(lb);
+        c->plan[ld].valid = false;
+        return fail(c, SGV_ERR_ARG,
+                    "sgv_set_ld_block: LD matrix %d block %d holds a finite entry outside the "
+                    "range of f32 (sgv_set_ld_precision 32)", ld, b);
+      }
+      HIPCHK(hipMemcpy2D(lb.f32() + lb.poff[g], sizeof(float) * lb.pw[g], hp, sizeof(float) * e,
+                         sizeof(float) * e, H, hipMemcpyHostToDevice));
+    }
   } else {
     for (size_t g = 0; g < lb.poff.size(); ++g) {
       const int64_t r0 = (int64_t)g * SYM_H, H = std::min<int64_t>(SYM_H, n - r0);
@@ -905,11 +976,13 @@ extern "C" int sgv_set_ld_block_csr(sgv_ctx* c, int ld, int b, const int64_t* in
   int64_t ext = round_up(SYM_H + bw, BAND_Q);
   if (ext >= n) ext = 0;   // the band is as wide as the triangle
   CHK(ld_alloc(c, ld, b, 1, ext));
-  const LdBlock& lb = c->ldb[ld][b];
+  LdBlock& lb = c->ldb[ld][b];
+  const bool f32 = lb.bits == 32;   // the panel assembled in f64, then narrowed behind it
   size_t pmax = 0;
   for (size_t g = 0; g < lb.poff.size(); ++g) pmax = std::max<size_t>(pmax, SYM_H * lb.pw[g]);
-  CHK(ensure_hstage(c, sizeof(double) * pmax));
+  CHK(ensure_hstage(c, (sizeof(double) + (f32 ? sizeof(float) : 0)) * pmax));
   double* hp = (double*)c->h_stage;
+  float* hf = (float*)(hp + pmax);
   for (size_t g = 0; g < lb.poff.size(); ++g) {
     const int64_t r0 = (int64_t)g * SYM_H, H = std::min<int64_t>(SYM_H, n - r0);
     const int64_t w = lb.pw[g];
@@ -918,8 +991,20 @@ extern "C" int sgv_set_ld_block_csr(sgv_ctx* c, int ld, int b, const int64_t* in
       for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) hp[(i - r0) * w + (indices[e] - r0)] += data[e];
     for (int64_t a = 0; a < H; ++a)   // the panel's diagonal block is stored in full
       for (int64_t d = a + 1; d < H; ++d) hp[d * w + a] = hp[a * w + d];
-    HIPCHK(hipMemcpyAsync(lb.ptr + lb.poff[g], hp, sizeof(double) * (size_t)(H * w),
-                          hipMemcpyHostToDevice, c->st));
+    if (f32) {
+      if (!narrow_f32(hp, hf, H * w)) {
+        free_block(lb);
+        c->plan[ld].valid = false;
+        return fail(c, SGV_ERR_ARG,
+                    "sgv_set_ld_block_csr: LD matrix %d block %d holds a finite entry outside the "
+                    "range of f32 (sgv_set_ld_precision 32)", ld, b);
+      }
+      HIPCHK(hipMemcpyAsync(lb.f32() + lb.poff[g], hf, sizeof(float) * (size_t)(H * w),
+                            hipMemcpyHostToDevice, c->st));
+    } else {
+      HIPCHK(hipMemcpyAsync(lb.ptr + lb.poff[g], hp, sizeof(double) * (size_t)(H * w),
+                            hipMemcpyHostToDevice, c->st));
+    }
     CHK(stream_wait(c));   // the pinned panel buffer is reused
   }
   std::fill(c->rx0_valid.begin(), c->rx0_valid.end(), 0);
@@ -941,10 +1026,20 @@ extern "C" int sgv_get_ld_block(sgv_ctx* c, int ld, int b, double* host, int64_t
   }
   if (lb.ext > 0)   // outside the band nothing is stored
     for (int64_t i = 0; i < n; ++i) std::memset(host + i * ld_host, 0, sizeof(double) * n);
+  if (lb.bits == 32) CHK(ensure_hstage(c, sizeof(float) * (size_t)SYM_H * (size_t)n));
   for (size_t g = 0; g < lb.poff.size(); ++g) {
     const int64_t r0 = (int64_t)g * SYM_H, H = std::min<int64_t>(SYM_H, n - r0);
+    const int64_t e = panel_ext(n, r0, lb.ext);
+    if (lb.bits == 32) {   // the stored floats, widened (exact)
+      float* hp = (float*)c->h_stage;
+      HIPCHK(hipMemcpy2D(hp, sizeof(float) * e, lb.f32() + lb.poff[g], sizeof(float) * lb.pw[g],
+                         sizeof(float) * e, H, hipMemcpyDeviceToHost));
+      for (int64_t i = 0; i < H; ++i)
+        for (int64_t j = 0; j < e; ++j) host[(r0 + i) * ld_host + r0 + j] = (double)hp[i * e + j];
+      continue;
+    }
     HIPCHK(hipMemcpy2D(host + r0 * ld_host + r0, sizeof(double) * ld_host, lb.ptr + lb.poff[g],
-                       sizeof(double) * lb.pw[g], sizeof(double) * panel_ext(n, r0, lb.ext), H,
+                       sizeof(double) * lb.pw[g], sizeof(double) * e, H,
                        hipMemcpyDeviceToHost));
   }
   for (int64_t i = 0; i < n; ++i) {          // mirror the part left of each panel

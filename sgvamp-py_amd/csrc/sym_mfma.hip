@@ -37,6 +37,8 @@
 // Dcol accumulates over all rows of the strip in registers; every order is fixed.
 #include "common.h"
 
+#include <type_traits>
+
 namespace sgv {
 
 #define MFMA4(a, b, c) __builtin_amdgcn_mfma_f64_4x4x4f64((a), (b), (c), 0, 0, 0)
@@ -71,6 +73,54 @@ __device__ __forceinline__ void lds_order() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// Stored element type T of the strip kernels' panels (k_sym_mfma, k_sym_mfma16;
+// sgv_set_ld_precision).  A fragment load is two consecutive columns of one row
+// per lane: 16 B of an f64 panel, 8 B of an f32 one, for the same 16 x 32
+// sub-tile in the same step order.  The prefetch ring keeps them as loaded (an
+// f32 ring is half the registers); the step that takes a fragment widens it to
+// f64 (v_cvt_f64_f32, exact) ahead of the LDS tile, and everything from there on
+// -- tile, MFMA chains, row and column partials -- is one text for both types.
+// So every chain of such a float instance (load form 1) sees the operands, in the
+// order, that the double instance sees on the widened matrix: its products are
+// bitwise equal.  The double case is the text as it was (the same code is
+// generated).  Load form 2 (below) is the one an f32 matrix runs by default.
+typedef float f2 __attribute__((ext_vector_type(2)));
+template <class T>
+struct Frag;
+template <>
+struct Frag<double> {
+  typedef d2 raw;
+  static __device__ __forceinline__ d2 widen(d2 v) { return v; }
+};
+template <>
+struct Frag<float> {
+  typedef f2 raw;
+  static __device__ __forceinline__ d2 widen(f2 v) { return d2{(double)v.x, (double)v.y}; }
+};
+// Load form LF = 2 (float panels only): 16 B per lane, a float4 of 4 consecutive
+// columns, one load per 64-column super-step feeding two 32-column steps -- half
+// the load instructions per element.  Sub-step e' of super-step S is step t = 2 S
+// + e', and its pair index p (the lane's place in the fragment, the tile and the
+// column accumulators) stands for chunk columns 64 S + 4 p + 2 e', + 1 instead
+// of 32 t + 2 p, + 1 (frag_col): the row-part operands, the loads and the column
+// stores take their columns from it, nothing else changes.  A row's terms are
+// then added in another fixed order: not bitwise the LF = 1 sums, still a function
+// of the block alone.
+typedef float f4 __attribute__((ext_vector_type(4)));
+// the form an f32 matrix runs: 2, faster than 1 on every line of the A/B (64 x
+// 15,625 -1...-5 % per pass, 8 x 15,625 -3...-9 %: DESIGN.md 4.6,
+// profiles/ld_f32/ldpass_ab.jsonl); 1 stays compiled as the bitwise pin
+constexpr int F32_FORM_DEFAULT = 2;
+template <int LF>
+__device__ __forceinline__ constexpr int frag_col(int t, int p) {
+  return LF == 2 ? 64 * (t >> 1) + 4 * p + 2 * (t & 1) : 32 * t + 2 * p;
+}
+// 32-column steps with a column below nrem (columns left from the wave's first)
+template <int LF>
+__device__ __forceinline__ int steps_upto(int nrem) {
+  return LF == 2 ? 2 * ((nrem + 63) / 64) : (nrem + 31) / 32;
+}
+
 constexpr int MF_CW = 512;   // chunk width (class 1 items)
 constexpr int MF_LDP = 34;   // k_sym_mfma16's staging row pitch (doubles): conflict-free both ways
 
@@ -103,7 +153,8 @@ constexpr int MF_LDP = 34;   // k_sym_mfma16's staging row pitch (doubles): conf
 // R fragment loads stay whole 128-B lines.  One box, alternating: the north
 // star -0.4...-0.8 % per pass, the 8-block share -1.4 %; at NG = 1 (8-B
 // operands) even to +0.4 %, so not there (profiles/r06/mf_sw_*.jsonl)
-template <int NG, int PD, bool RAG = false, bool DEF = false, bool PP = false>
+template <int NG, int PD, bool RAG = false, bool DEF = false, bool PP = false, class T = double,
+          int LF = 1>
 __global__ __launch_bounds__(256, 2) void k_sym_mfma(const SymStrip* __restrict__ strips,
                                                      const SymItem* __restrict__ sitems,
                                                      const double* __restrict__ pk, int ncol,
@@ -116,6 +167,10 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma(const SymStrip* __restrict_
   static_assert(PD >= 1 && PD <= NT && NT % PD == 0, "prefetch depth divides the steps");
   constexpr int RW = 4 * NG;       // row-sum stride of wrow
   constexpr bool SWZ = NG == 2;
+  constexpr bool W4 = LF == 2;        // 16-B loads of float panels (frag_col)
+  static_assert(!W4 || (sizeof(T) == 4 && PD == 2 && NT % 2 == 0), "LF = 2: float, two super-steps");
+  typedef typename std::conditional<W4, f4, typename Frag<T>::raw>::type RV;   // a fragment as loaded
+  constexpr int RD = W4 ? NT / 2 : PD;   // ring depth (LF = 2: in super-steps, the same bytes)
   __shared__ __attribute__((aligned(16))) double rowbuf[NW * SYM_H * RW];   // wrow
   // the per-wave transpose tile: 16 rows x 32 columns, 16-B piece (row r, pair
   // p) at slot 16 r + (p ^ (r & 3)) -- unpadded (4 KiB, so the 64 KiB of row
@@ -142,7 +197,8 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma(const SymStrip* __restrict_
   // read, so every kept sum is bitwise the same; nor do the column MFMAs of the
   // diagonal-block waves of a diagonal panel (B = 0 there).  The loads stay, so
   // the load count is the same on every path.
-  const int nta = min(NT, max(0, (ncc - cw0 + 31) / 32));
+  const int nta = W4 ? min(NT, max(0, steps_upto<LF>(ncc - cw0)))
+                     : min(NT, max(0, (ncc - cw0 + 31) / 32));
   double* sb = stg[wid];
 
   // row-part B operands: P at this wave's columns, reused by every row group
@@ -163,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma(const SymStrip* __restrict_
   for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-      const int col = cw0 + 32 * t + 2 * pc + e;
+      const int col = W4 ? cw0 + frag_col<LF>(t, pc) + e : cw0 + 32 * t + 2 * pc + e;
       double v[NG];
       ld_prow(c0 + (col < ncc ? col : 0), v);
 #pragma unroll
@@ -178,21 +234,22 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma(const SymStrip* __restrict_
       for (int q = 0; q < NG; ++q) dcol[t][e][q] = 0.0;
 
   // fragment loads of step (g, t) of a panel (b0 = its element (r0, c0)), 16 B
-  // per lane, branch-free: a row past H clamps (its P is 0), a column past the
+  // per lane (8 B of an f32 panel; strides and offsets in elements), branch-free: a row past H clamps (its P is 0), a column past the
   // chunk loads column 0 (finite; it meets a zero B in the row part and is never
   // read from the column part).  The base is an opaque integer: a pointer select
   // is turned back into a branch with one load per side.  Past the strip's last
   // row group the caller passes the cache-resident Pk with stride 0 (a dummy
   // fetch: the load count is the same on every path, so the compiler never
   // drains vmcnt(0) at a branch join or the row-group loop head).
-  auto load_cf = [&](uint64_t b0, int64_t ws, int H, int nci, int g, int t, d2* cf) {
+  // (LF = 2: t counts super-steps, one float4 of columns 64 t + 4 lo ..)
+  auto load_cf = [&](uint64_t b0, int64_t ws, int H, int nci, int g, int t, RV* cf) {
     asm volatile("" : "+s"(b0));
-    const int xc = cw0 + 32 * t + 2 * lo;
+    const int xc = W4 ? cw0 + 64 * t + 4 * lo : cw0 + 32 * t + 2 * lo;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const int rB = 16 * g + 4 * (SWZ ? a ^ (bq & 2) : a) + hi;
-      const double* row = (const double*)b0 + (int64_t)(rB < H ? rB : H - 1) * ws;
-      cf[a] = ldg_nt((const d2*)(row + (xc < (RAG ? nci : ncc) ? xc : 0)));
+      const T* row = (const T*)b0 + (int64_t)(rB < H ? rB : H - 1) * ws;
+      cf[a] = ldg_nt((const RV*)(row + (xc < (RAG ? nci : ncc) ? xc : 0)));
     }
   };
   // column-part B operands of row group g of a panel (first row r0): P at its
@@ -208,11 +265,11 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma(const SymStrip* __restrict_
       for (int q = 0; q < NG; ++q) bc[a][q] = (rB < H && !zero) ? v[q] : 0.0;
     }
   };
-  auto pbase = [&](const SymItem& x) { return (uint64_t)(x.P + (x.c0 - x.r0)); };
+  auto pbase = [&](const SymItem& x) { return (uint64_t)((const T*)x.P + (x.c0 - x.r0)); };
   // a band panel's item narrower than the strip: its columns past nci (never
   // loaded: the loads above took column 0) read as zero
   auto band_zero = [&](int nci, int t, d2* cf) {
-    const int xc = cw0 + 32 * t + 2 * lo;
+    const int xc = W4 ? cw0 + frag_col<LF>(t, lo) : cw0 + 32 * t + 2 * lo;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       cf[a].x = xc < nci ? cf[a].x : 0.0;
@@ -222,10 +279,10 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma(const SymStrip* __restrict_
 
   uint64_t curb = pbase(cur);
   // ring of PD steps in flight per wave
-  d2 cfq[PD][4];
+  RV cfq[RD][4];
   double bcn[SWZ ? 1 : 4][NG];
 #pragma unroll
-  for (int p = 0; p < PD; ++p) load_cf(curb, cur.w, cur.H, cur.nc, 0, p, cfq[p]);
+  for (int p = 0; p < RD; ++p) load_cf(curb, cur.w, cur.H, cur.nc, 0, p, cfq[p]);
   load_bcol(cur.r0, cur.H, dhalf && cur.r0 == c0, 0, bcn);
 
 #pragma unroll 1
@@ -262,21 +319,39 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma(const SymStrip* __restrict_
       // step wholly past its stored end adds only zeros -- skipped like the
       // steps past the chunk; per panel, so the deferred row MFMAs (DEF) know
       // the item's last active step
-      const int ntp = RAG ? min(nta, max(0, (cur.nc - cw0 + 31) / 32)) : nta;
+      const int ntp = RAG ? min(nta, max(0, W4 ? steps_upto<LF>(cur.nc - cw0) : (cur.nc - cw0 + 31) / 32)) : nta;
+      d2 cfw[W4 ? 2 : 1][4];                             // LF = 2: a super-step's two steps, widened
       d2 rfb[DEF ? 2 : 1][4];                            // row fragments (DEF: this and the previous step)
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         d2 cf[4];
         d2* rf = rfb[DEF ? (t & 1) : 0];
         const int slot = t % PD;                       // compile-time after unrolling
+        if constexpr (W4) {
+          // a super-step's float4s are taken (and widened) at its first step, and
+          // the same super-step of the next row group goes out in their place
+          if ((t & 1) == 0) {
 #pragma unroll
-        for (int a = 0; a < 4; ++a) cf[a] = cfq[slot][a];
+            for (int a = 0; a < 4; ++a) {
+              const f4 v = cfq[t >> 1][a];
+              cfw[0][a] = d2{(double)v.x, (double)v.y};
+              cfw[1][a] = d2{(double)v.z, (double)v.w};
+            }
+            load_cf(gb, gw, gH, gnc, gn, t >> 1, cfq[t >> 1]);
+            if (t + PD == NT) load_bcol(gr0, gH, gz, gn, bcn);
+          }
+#pragma unroll
+          for (int a = 0; a < 4; ++a) cf[a] = cfw[t & 1][a];
+        } else {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) cf[a] = Frag<T>::widen(cfq[slot][a]);
         // step + PD goes out here, ahead of this step's LDS and MFMA work
         if (t + PD < NT) {
           load_cf(curb, cur.w, cur.H, cur.nc, g, t + PD, cfq[slot]);
         } else {
           load_cf(gb, gw, gH, gnc, gn, t + PD - NT, cfq[slot]);
           if (t + PD == NT) load_bcol(gr0, gH, gz, gn, bcn);
+        }
         }
         if (t >= ntp) continue;                        // wave-uniform: past the chunk / item
         if (RAG && cur.nc < ncc) band_zero(cur.nc, t, cf);   // uniform: a band item's stored end
@@ -394,7 +469,10 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma(const SymStrip* __restrict_
       double* out = colpart + ((int64_t)sp.slot * ncol + cc) * MF_CW;
 #pragma unroll
       for (int t = 0; t < NT; ++t)
-        *(d2*)(out + cw0 + 32 * t + 2 * pc) = d2{dcol[t][0][q], dcol[t][1][q]};
+        if constexpr (W4)
+          *(d2*)(out + cw0 + frag_col<LF>(t, pc)) = d2{dcol[t][0][q], dcol[t][1][q]};
+        else
+          *(d2*)(out + cw0 + 32 * t + 2 * pc) = d2{dcol[t][0][q], dcol[t][1][q]};
     }
   }
   MF_TRACE_END
@@ -511,7 +589,7 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_pair(const SymStrip* __rest
       for (int q = 0; q < NG; ++q) bc[a][q] = (rB < H && !zero) ? v[q] : 0.0;
     }
   };
-  auto pbase = [&](const SymItem& x) { return (uint64_t)(x.P + (x.c0 - x.r0)); };
+  auto pbase = [&](const SymItem& x) { return (uint64_t)((const double*)x.P + (x.c0 - x.r0)); };
 
   uint64_t curb = pbase(cur);
   d2 cfq[PD][4];
@@ -779,7 +857,7 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_wide(const SymStrip* __rest
       for (int q = 0; q < NG; ++q) bc[a][q] = (rB < H && !zero) ? v[q] : 0.0;
     }
   };
-  auto pbase = [&](const SymItem& x) { return (uint64_t)(x.P + (x.c0 - x.r0)); };
+  auto pbase = [&](const SymItem& x) { return (uint64_t)((const double*)x.P + (x.c0 - x.r0)); };
 
   uint64_t curb = pbase(cur);
   d2 cfq[PD][4];
@@ -945,7 +1023,7 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 // TB: the row-part B operands of the last TB steps kept in LDS (8 TB doubles per
 // lane, 4 TB KiB per wave, read back per step as 4 x 16 B) instead of registers
-template <int PD, bool RAG = false, int TB = 0>
+template <int PD, bool RAG = false, int TB = 0, class T = double, int LF = 1>
 __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restrict__ strips,
                                                      const SymItem* __restrict__ sitems,
                                                      const double* __restrict__ pk, int ncol,
@@ -955,6 +1033,10 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
   constexpr int LDP = MF_LDP;
   constexpr int MF_WC = MF_CW / 4; // columns per wave
   constexpr int MF_NT = MF_WC / 32;
+  constexpr bool W4 = LF == 2;        // 16-B loads of float panels (frag_col), as k_sym_mfma
+  static_assert(!W4 || (sizeof(T) == 4 && PD == 2 && MF_NT % 2 == 0), "LF = 2: float, two super-steps");
+  typedef typename std::conditional<W4, f4, typename Frag<T>::raw>::type RV;   // a fragment as loaded
+  constexpr int RD = W4 ? MF_NT / 2 : PD;
   __shared__ double red[2][4][256];
   __shared__ __attribute__((aligned(16))) double stg[4][16 * LDP];
   constexpr bool BL = TB > 0;
@@ -969,7 +1051,8 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
   const double* pkb = pk + (int64_t)cur.voff * 16;    // Pk of this block (block-relative index)
   const int cw0 = wid * MF_WC;                         // first chunk column of this wave
   const bool dhalf = cw0 < SYM_H;
-  const int nta = min(MF_NT, max(0, (ncc - cw0 + 31) / 32));   // as k_sym_mfma
+  const int nta = W4 ? min(MF_NT, max(0, steps_upto<LF>(ncc - cw0)))
+                     : min(MF_NT, max(0, (ncc - cw0 + 31) / 32));   // as k_sym_mfma
 
   double* sb = stg[wid];
   // row-part B operands (P at this wave's columns), reused by every row group
@@ -980,7 +1063,8 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
     for (int s = 0; s < 4; ++s)
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
-        const int col = cw0 + 32 * t + 8 * s + 2 * hi + e;
+        const int col = W4 ? cw0 + frag_col<LF>(t, 4 * s + hi) + e   // pair 4 s + hi
+                           : cw0 + 32 * t + 8 * s + 2 * hi + e;
         const double v = ldg(pkb + (int64_t)(c0 + (col < ncc ? col : 0)) * 16 + lo);
         if (t < MF_NT - TB) brow[t < MF_NT - TB ? t : 0][s][e] = col < ncc ? v : 0.0;
         else if constexpr (BL) bls[wid][(t - (MF_NT - TB)) * 4 + s][lane][e] = col < ncc ? v : 0.0;
@@ -989,18 +1073,18 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
 #pragma unroll
   for (int t = 0; t < MF_NT; ++t) dcol[t][0] = dcol[t][1] = d4{0.0, 0.0, 0.0, 0.0};
 
-  auto load_cf = [&](uint64_t b0, int64_t ws, int H, int nci, int g, int t, d2* cf) {
+  auto load_cf = [&](uint64_t b0, int64_t ws, int H, int nci, int g, int t, RV* cf) {
     asm volatile("" : "+s"(b0));
-    const int xc = cw0 + 32 * t + 2 * lo;
+    const int xc = W4 ? cw0 + 64 * t + 4 * lo : cw0 + 32 * t + 2 * lo;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const int rB = 16 * g + 4 * a + hi;
-      const double* row = (const double*)b0 + (int64_t)(rB < H ? rB : H - 1) * ws;
-      cf[a] = ldg_nt((const d2*)(row + (xc < (RAG ? nci : ncc) ? xc : 0)));
+      const T* row = (const T*)b0 + (int64_t)(rB < H ? rB : H - 1) * ws;
+      cf[a] = ldg_nt((const RV*)(row + (xc < (RAG ? nci : ncc) ? xc : 0)));
     }
   };
   auto band_zero = [&](int nci, int t, d2* cf) {   // as k_sym_mfma
-    const int xc = cw0 + 32 * t + 2 * lo;
+    const int xc = W4 ? cw0 + frag_col<LF>(t, lo) : cw0 + 32 * t + 2 * lo;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       cf[a].x = xc < nci ? cf[a].x : 0.0;
@@ -1015,14 +1099,14 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
       bc[a] = (rB < H && !zero) ? v : 0.0;
     }
   };
-  auto pbase = [&](const SymItem& x) { return (uint64_t)(x.P + (x.c0 - x.r0)); };
+  auto pbase = [&](const SymItem& x) { return (uint64_t)((const T*)x.P + (x.c0 - x.r0)); };
 
   static_assert(PD >= 1 && PD <= MF_NT && MF_NT % PD == 0, "prefetch depth divides the steps");
   uint64_t curb = pbase(cur);
-  d2 cfq[PD][4];                                       // ring of PD steps in flight per wave
+  RV cfq[RD][4];                                       // ring of PD steps in flight per wave
   double bcn[4];
 #pragma unroll
-  for (int p = 0; p < PD; ++p) load_cf(curb, cur.w, cur.H, cur.nc, 0, p, cfq[p]);
+  for (int p = 0; p < RD; ++p) load_cf(curb, cur.w, cur.H, cur.nc, 0, p, cfq[p]);
   load_bcol(cur.r0, cur.H, dhalf && cur.r0 == c0, 0, bcn);
 
   int gg = 0;
@@ -1047,12 +1131,27 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
       for (int a = 0; a < 4; ++a) bcol[a] = bcn[a];
       d4 drow0 = d4{0.0, 0.0, 0.0, 0.0}, drow1 = drow0;
       const bool colz = dhalf && cur.r0 == c0;
+      d2 cfw[W4 ? 2 : 1][4];                           // LF = 2: a super-step's two steps, widened
 #pragma unroll
       for (int t = 0; t < MF_NT; ++t) {
         d2 cf[4], rf[4];
         const int slot = t % PD;                       // compile-time after unrolling
+        if constexpr (W4) {   // as k_sym_mfma
+          if ((t & 1) == 0) {
 #pragma unroll
-        for (int a = 0; a < 4; ++a) cf[a] = cfq[slot][a];
+            for (int a = 0; a < 4; ++a) {
+              const f4 v = cfq[t >> 1][a];
+              cfw[0][a] = d2{(double)v.x, (double)v.y};
+              cfw[1][a] = d2{(double)v.z, (double)v.w};
+            }
+            load_cf(gb, gw, gH, gnc, gn, t >> 1, cfq[t >> 1]);
+            if (t + PD == MF_NT) load_bcol(gr0, gH, gz, gn, bcn);
+          }
+#pragma unroll
+          for (int a = 0; a < 4; ++a) cf[a] = cfw[t & 1][a];
+        } else {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) cf[a] = Frag<T>::widen(cfq[slot][a]);
         // step + PD goes out here, ahead of this step's LDS and MFMA work
         if (t + PD < MF_NT) {
           load_cf(curb, cur.w, cur.H, cur.nc, g, t + PD, cfq[slot]);
@@ -1060,8 +1159,9 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
           load_cf(gb, gw, gH, gnc, gn, t + PD - MF_NT, cfq[slot]);
           if (t + PD == MF_NT) load_bcol(gr0, gH, gz, gn, bcn);
         }
+        }
         if (t >= nta) continue;
-        if (RAG && cw0 + 32 * t >= cur.nc) continue;   // as k_sym_mfma
+        if (RAG && cw0 + (W4 ? 64 * (t >> 1) : 32 * t) >= cur.nc) continue;   // as k_sym_mfma
         if (RAG && cur.nc < ncc) band_zero(cur.nc, t, cf);
         lds_order();                                   // previous step's tile reads done
 #pragma unroll
@@ -1112,7 +1212,10 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
     for (int t = 0; t < MF_NT; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        *(d2*)(out + cw0 + 32 * t + 2 * (hi + 4 * r)) = d2{dcol[t][0][r], dcol[t][1][r]};
+        if constexpr (W4)
+          *(d2*)(out + cw0 + frag_col<LF>(t, hi + 4 * r)) = d2{dcol[t][0][r], dcol[t][1][r]};
+        else
+          *(d2*)(out + cw0 + 32 * t + 2 * (hi + 4 * r)) = d2{dcol[t][0][r], dcol[t][1][r]};
   }
 }
 
@@ -1298,12 +1401,34 @@ __global__ __launch_bounds__(256) void k_pack(PassArgs pa, int ncol, int64_t mpa
 // once per row group the model's choice holds at 5-8 columns too: the 8-block
 // share -2...-8 %, 4 x 25,000 -2.6 % per 8-column pass; launches it does not
 // pick run +1.4...+9 % with the pair form (profiles/r06/pair58_*.jsonl)
+// f32 (the tables' panels hold floats): the float instances of the same two
+// 4-wave kernels -- RAG for band plans, DEF otherwise; there is no float pair form
+// SGV_F32_FORM (A/B, with SGV_AB=1): the float kernels' load form -- 1 = 8 B per
+// lane (bitwise the f64 strips on the widened matrix), 2 = 16 B per lane
+// (frag_col); read per launch (a getenv)
+static int f32_form() {
+  const char* e = ab_env("SGV_F32_FORM");
+  return (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : F32_FORM_DEFAULT;
+}
+
 template <int NG, bool PP = false>
 static void launch_mf(const SymStrip* d_strips, int nstrips, const SymItem* d_sitems,
                       const double* d_pk, int nc, double* rowpart, double* colpart,
-                      const int* run, int pks, bool ragged, int pair, hipStream_t st) {
+                      const int* run, int pks, bool ragged, int pair, bool f32, hipStream_t st) {
   // prefetch depth 2 measured best (PD 1/2/4: 11.64/11.16/12.27 ms at NC=4, M=1e6)
-  if (ragged)
+  if (f32 && f32_form() == 2 && ragged)
+    hipLaunchKernelGGL((k_sym_mfma<NG, 2, true, false, PP, float, 2>), dim3(nstrips), dim3(256), 0,
+                       st, d_strips, d_sitems, d_pk, nc, rowpart, colpart, run, pks);
+  else if (f32 && f32_form() == 2)
+    hipLaunchKernelGGL((k_sym_mfma<NG, 2, false, true, PP, float, 2>), dim3(nstrips), dim3(256), 0,
+                       st, d_strips, d_sitems, d_pk, nc, rowpart, colpart, run, pks);
+  else if (f32 && ragged)
+    hipLaunchKernelGGL((k_sym_mfma<NG, 2, true, false, PP, float>), dim3(nstrips), dim3(256), 0,
+                       st, d_strips, d_sitems, d_pk, nc, rowpart, colpart, run, pks);
+  else if (f32)
+    hipLaunchKernelGGL((k_sym_mfma<NG, 2, false, true, PP, float>), dim3(nstrips), dim3(256), 0,
+                       st, d_strips, d_sitems, d_pk, nc, rowpart, colpart, run, pks);
+  else if (ragged)
     hipLaunchKernelGGL((k_sym_mfma<NG, 2, true, false, PP>), dim3(nstrips), dim3(256), 0, st,
                        d_strips, d_sitems, d_pk, nc, rowpart, colpart, run, pks);
   else if (pair >= 1)
@@ -1338,8 +1463,11 @@ hipError_t launch_pk(const PassArgs& pa, int nc, int64_t mpad, double* d_pk, hip
 
 hipError_t launch_sym_mfma(int nc, const SymStrip* d_strips, int nstrips, const SymItem* d_sitems,
                            const PassArgs& pa, const double* d_pk, double* rowpart,
-                           double* colpart, bool ragged, int pair, hipStream_t st) {
+                           double* colpart, bool ragged, int pair, int bits, hipStream_t st) {
   if (nc < 1 || nc > 16) return hipErrorInvalidValue;
+  if (bits != 64 && bits != 32) return hipErrorInvalidValue;
+  const bool f32 = bits == 32;
+  if (f32 && pair) return hipErrorInvalidValue;   // no float instance of the pair form
   if (nstrips <= 0) return hipSuccess;
   const int pks = nc > 8 ? 16 : nc <= 4 ? 4 : 8;
   // 9..16 columns: one 16x16x4 group beats three/four 4x4x4 groups (register
@@ -1358,17 +1486,29 @@ hipError_t launch_sym_mfma(int nc, const SymStrip* d_strips, int nstrips, const 
   // issues cost more than they save; the spill-free form kept is the row
   // operands of the last step(s) in LDS (below).
   switch ((nc + 3) / 4) {
-    case 1: launch_mf<1>(d_strips, nstrips, d_sitems, d_pk, nc, rowpart, colpart, pa.run, pks, ragged, pair, st); break;
+    case 1: launch_mf<1>(d_strips, nstrips, d_sitems, d_pk, nc, rowpart, colpart, pa.run, pks, ragged, pair, f32, st); break;
     case 2:   // Pk paired (strip_pk_paired)
       launch_mf<2, true>(d_strips, nstrips, d_sitems, d_pk, nc, rowpart, colpart, pa.run, pks,
-                         ragged, pair, st);
+                         ragged, pair, f32, st);
       break;
     default:
       // the row operands of the last steps in LDS, so nothing spills (256 VGPRs
       // with 3 / 7 spilled before): band plans the last 2 steps (-0.6 % per
       // 16-column band pass), dense plans the last one (even; 2 steps there +2 %)
       // -- profiles/r06/mf16_bl_*.jsonl, mf16_tb_*.jsonl; products bitwise equal
-      if (ragged)
+      if (f32 && f32_form() == 2 && ragged)
+        hipLaunchKernelGGL((k_sym_mfma16<2, true, 2, float, 2>), dim3(nstrips), dim3(256), 0, st,
+                           d_strips, d_sitems, d_pk, nc, rowpart, colpart, pa.run);
+      else if (f32 && f32_form() == 2)
+        hipLaunchKernelGGL((k_sym_mfma16<2, false, 1, float, 2>), dim3(nstrips), dim3(256), 0, st,
+                           d_strips, d_sitems, d_pk, nc, rowpart, colpart, pa.run);
+      else if (f32 && ragged)
+        hipLaunchKernelGGL((k_sym_mfma16<2, true, 2, float>), dim3(nstrips), dim3(256), 0, st,
+                           d_strips, d_sitems, d_pk, nc, rowpart, colpart, pa.run);
+      else if (f32)
+        hipLaunchKernelGGL((k_sym_mfma16<2, false, 1, float>), dim3(nstrips), dim3(256), 0, st,
+                           d_strips, d_sitems, d_pk, nc, rowpart, colpart, pa.run);
+      else if (ragged)
         hipLaunchKernelGGL((k_sym_mfma16<2, true, 2>), dim3(nstrips), dim3(256), 0, st, d_strips,
                            d_sitems, d_pk, nc, rowpart, colpart, pa.run);
       else

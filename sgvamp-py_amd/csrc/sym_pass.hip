@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256, OCC) void k_sym_pass(const SymItem* __restrict
     for (int r = 0; r < RWI; ++r) {
       const int rr = rbase + r;
       const bool ok = rr < it.H;
-      rp[r] = it.P + (int64_t)(ok ? rr : it.H - 1) * it.w + (it.c0 - it.r0);
+      rp[r] = (const double*)it.P + (int64_t)(ok ? rr : it.H - 1) * it.w + (it.c0 - it.r0);
 #pragma unroll
       for (int c = 0; c < NC; ++c) prow[r][c] = ok ? pp[c][it.r0 + rr] : 0.0;
     }

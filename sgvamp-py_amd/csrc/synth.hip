@@ -87,8 +87,11 @@ hipError_t launch_geno_G(uint64_t seed, int64_t gm0, int n, int nsamp, int ldg,
 
 // R = G G^T (n x n, symmetric; upper tiles computed, mirrored).  64x64 tiles,
 // 256 threads x (4 x 4) outputs, K-steps of 16 staged through LDS.
+// T: the stored element type; float (packed blocks stored as f32) rounds the
+// f64 sum once, to nearest even, on store
+template <class T>
 __global__ __launch_bounds__(256) void k_syrk_nt(const double* __restrict__ G, int n, int kpad,
-                                                 int ldg, double* __restrict__ R, int64_t lda,
+                                                 int ldg, T* __restrict__ R, int64_t lda,
                                                  int packed, const int64_t* __restrict__ poff,
                                                  const int64_t* __restrict__ pw) {
   const int tj = blockIdx.x, ti = blockIdx.y;
@@ -132,24 +135,30 @@ __global__ __launch_bounds__(256) void k_syrk_nt(const double* __restrict__ G, i
       const int i = i0 + ty + 16 * a, j = j0 + tx + 16 * b;
       if (i < n && j < n) {
         if (packed) {
-          double* p = sym_addr(R, poff, pw, i, j);
-          if (p) *p = acc[a][b];
+          T* p = sym_addr(R, poff, pw, i, j);
+          if (p) *p = (T)acc[a][b];
           p = sym_addr(R, poff, pw, j, i);
-          if (p) *p = acc[a][b];
+          if (p) *p = (T)acc[a][b];
         } else {
-          R[(int64_t)i * lda + j] = acc[a][b];
-          R[(int64_t)j * lda + i] = acc[a][b];
+          R[(int64_t)i * lda + j] = (T)acc[a][b];
+          R[(int64_t)j * lda + i] = (T)acc[a][b];
         }
       }
     }
 }
 
-hipError_t launch_syrk_nt(const double* d_G, int n, int nsamp, int ldg, double* d_R, int64_t lda,
-                          int packed, const int64_t* d_poff, const int64_t* d_pw, hipStream_t st) {
+hipError_t launch_syrk_nt(const double* d_G, int n, int nsamp, int ldg, void* d_R, int64_t lda,
+                          int packed, const int64_t* d_poff, const int64_t* d_pw, int bits,
+                          hipStream_t st) {
   const int nt = (n + 63) / 64;
   const int kpad = (nsamp + 15) / 16 * 16;  // <= ldg, zero padded
-  hipLaunchKernelGGL(k_syrk_nt, dim3(nt, nt), dim3(256), 0, st, d_G, n, kpad, ldg, d_R, lda,
-                     packed, d_poff, d_pw);
+  if (bits == 32 && !packed) return hipErrorInvalidValue;   // f32 is a packed layout only
+  if (bits == 32)
+    hipLaunchKernelGGL(k_syrk_nt<float>, dim3(nt, nt), dim3(256), 0, st, d_G, n, kpad, ldg,
+                       (float*)d_R, lda, packed, d_poff, d_pw);
+  else
+    hipLaunchKernelGGL(k_syrk_nt<double>, dim3(nt, nt), dim3(256), 0, st, d_G, n, kpad, ldg,
+                       (double*)d_R, lda, packed, d_poff, d_pw);
   return hipGetLastError();
 }
 

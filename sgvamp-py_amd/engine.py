@@ -413,6 +413,19 @@ class Engine:
         """True: symmetric blocks set/generated from now on are stored packed."""
         self.ctx.sgv_set_ld_packing(int(bool(packed)))
 
+    def set_ld_precision(self, bits):
+        """64 (default) or 32: the element type of packed blocks (triangle, band)
+        set or generated from now on.  32 rounds R once, on store, to the nearest
+        f32 and halves the stored bytes; every product and sum stays f64.  A block
+        stored as the full square stays f64."""
+        self.ctx.sgv_set_ld_precision(int(bits))
+
+    def ld_block_precision(self, ld, b_global):
+        """64 or 32: the element type LD matrix ld's block b_global is stored in."""
+        f = np.zeros(1, dtype=np.int32)
+        self.ctx.sgv_ld_block_precision(int(ld), b_global - self.b0, hb.iptr(f))
+        return int(f[0])
+
     def ld_block_format(self, ld, b_global):
         f = np.zeros(1, dtype=np.int32)
         self.ctx.sgv_ld_block_format(int(ld), b_global - self.b0, hb.iptr(f))

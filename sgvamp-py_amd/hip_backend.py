@@ -59,6 +59,8 @@ _SIGS = {
     "sgv_set_ld_block_csr": [_vp, ctypes.c_int, ctypes.c_int, _c_i64_p, _c_i64_p, _c_dbl_p],
     "sgv_set_ld_packing": [_vp, ctypes.c_int],
     "sgv_ld_block_format": [_vp, ctypes.c_int, ctypes.c_int, _c_int_p],
+    "sgv_set_ld_precision": [_vp, ctypes.c_int],
+    "sgv_ld_block_precision": [_vp, ctypes.c_int, ctypes.c_int, _c_int_p],
     "sgv_ld_stored_bytes": [_vp, ctypes.c_int, _c_dbl_p],
     "sgv_set_ld_coupling": [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dbl_p],
     "sgv_set_ridge": [_vp, ctypes.c_double],

@@ -65,6 +65,8 @@ def build_parser():
     parser.add_argument("--device", help="HIP device (default: the node-local rank)", default=None)
     parser.add_argument("--gpus", help="GPU ranks to start on this node (default: the launcher's "
                         "world size, else 1)", default=None)
+    parser.add_argument("--ld-precision", choices=["f64", "f32"], default="f64",
+                        help="Element type packed LD blocks are stored in: f32 rounds R once, at load, to the nearest f32, half the LD memory; all arithmetic stays f64 (the exact f64 solve of R perturbed by <= 2^-24 relative per entry)")
     return parser
 
 
@@ -203,7 +205,8 @@ def main(argv=None):
     sgv = VAMP(N=N_list, Nt=Nt, M=M, K=K, rho=rho, gam1=gam1, gamw=gamw, a=a,
                prior_vars=prior_vars_list, prior_probs=prior_probs_list, out_dir=out_dir,
                out_name=out_name, comm=comm, seed=seed,
-               device=None if args.device is None else int(args.device))
+               device=None if args.device is None else int(args.device),
+               ld_precision=args.ld_precision)
     if rank == 0:
         logging.info("...Running sgVAMP\n")
     ts = time.time()

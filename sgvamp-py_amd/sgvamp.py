@@ -302,10 +302,13 @@ def common_partition(size_lists):
     return [int(b - a) for a, b in zip(common[:-1], common[1:])]
 
 
+LD_PRECISIONS = {"f64": 64, "f32": 32}   # ld_precision -> Engine.set_ld_precision bits
+
+
 class VAMP:
     def __init__(self, N, Nt, M, K, rho, gamw, gam1, a, prior_vars, prior_probs, out_dir,
                  out_name, comm=None, seed=None, device=None, write_files=True, ld_packing=True,
-                 exchange=None, mfma_min=None, rs_recurrence=None):
+                 exchange=None, mfma_min=None, rs_recurrence=None, ld_precision="f64"):
         # src/sgvamp.py:15-31
         self.eps = 1e-32
         self.K = int(K)
@@ -338,6 +341,14 @@ class VAMP:
         self.exchange = exchange
         self.write_files = write_files
         self.ld_packing = ld_packing   # packed symmetric LD storage for symmetric blocks
+        # "f32": packed LD blocks keep R rounded once to f32 (half the LD memory);
+        # all arithmetic stays f64.  Only packed blocks have an f32 form.
+        if ld_precision not in LD_PRECISIONS:
+            raise ValueError("ld_precision must be 'f64' or 'f32', not %r" % (ld_precision,))
+        if ld_precision == "f32" and not ld_packing:
+            raise ValueError("ld_precision='f32' needs ld_packing=True: only packed LD blocks "
+                             "are stored as f32")
+        self.ld_precision = ld_precision
         self.mfma_min = mfma_min       # None: library default (f64 MFMA pass from 3 RHS)
         self.rs_recurrence = rs_recurrence   # None: library default (R_s x carried, no gamw pass)
         self.gam = None
@@ -431,6 +442,7 @@ class VAMP:
         self.engine = eng = Engine(sizes, K, ld_of, comm=self.comm, device=self.device,
                                           exchange=self.exchange)
         eng.set_ld_packing(self.ld_packing)
+        eng.set_ld_precision(LD_PRECISIONS[self.ld_precision])
         if self.mfma_min is not None:
             eng.set_mfma_min(self.mfma_min)
         if self.rs_recurrence is not None:

@@ -80,8 +80,12 @@ def _write_ld(eng, ld, sizes, prefix):
 
 
 def simulate(out, N, M, K=2, h2=0.8, lam=0.5, block_size=None, shared_ld=False, seed=2025,
-             device=None):
-    """Writes the files listed in the module docstring; returns their paths."""
+             device=None, ld_precision="f64"):
+    """Writes the files listed in the module docstring; returns their paths.
+    ld_precision "f32": the generator keeps R = G G^T (computed in f64) rounded
+    to f32 on the device, half the memory; the files hold those values as f64."""
+    if ld_precision not in ("f64", "f32"):
+        raise ValueError("ld_precision must be 'f64' or 'f32', not %r" % (ld_precision,))
     bs = int(block_size or M)
     sizes = [bs] * (M // bs) + ([M % bs] if M % bs else [])
     rs = np.random.RandomState(seed)
@@ -95,6 +99,7 @@ def simulate(out, N, M, K=2, h2=0.8, lam=0.5, block_size=None, shared_ld=False, 
     geno_seed = [seed + 1 + 7919 * ld for ld in range(nld)]   # one genotype stream per LD
     eng = Engine(sizes, K=K, ld_of=ld_of, device=device)
     try:
+        eng.set_ld_precision(32 if ld_precision == "f32" else 64)
         g = [eng.synth_ld_g(ld, geno_seed[ld], N, beta).sum(axis=0) for ld in range(nld)]
         ld_path = [_write_ld(eng, ld, sizes, out + ("_R" if shared_ld else "_%d_R" % ld))
                    for ld in range(nld)]
@@ -130,12 +135,16 @@ def main(argv=None):
     p.add_argument("--shared-ld", help="1: all cohorts share one genotype draw (one LD)", default=0)
     p.add_argument("--seed", help="beta, genotype and noise seed", default=2025)
     p.add_argument("--device", help="HIP device", default=None)
+    p.add_argument("--ld-precision", choices=["f64", "f32"], default="f64",
+                   help="Element type the on-device generator stores R in: f32 rounds G G^T "
+                        "(computed in f64) once, on store, and halves the LD memory")
     a = p.parse_args(argv)
     print("...Simulating data for sgVAMP\n")
     paths = simulate(a.out, int(a.N), int(a.M), K=int(a.K), h2=float(a.h2), lam=float(a.lam),
                      block_size=int(a.block_size) if a.block_size else None,
                      shared_ld=bool(int(a.shared_ld)), seed=int(a.seed),
-                     device=int(a.device) if a.device is not None else None)
+                     device=int(a.device) if a.device is not None else None,
+                     ld_precision=a.ld_precision)
     print("main.py inputs: --ld-files %s --r-files %s --bim-files %s --true-signal-file %s"
           % (",".join(paths["ld"]), ",".join(paths["r"]), ",".join(paths["bim"]), paths["beta"]))
 

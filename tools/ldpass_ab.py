@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--ncols", default="4,8")
     ap.add_argument("--nsamp", type=int, default=2000)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--ld-precision", default="f64", choices=["f64", "f32"],
+                    help="element type of the packed blocks (Engine.set_ld_precision)")
     ap.add_argument("--lib", default=None, help="A/B of builds: load this libsgvamp_hip.so")
     ap.add_argument("--rhs", default="normal", choices=["normal", "zero", "ones"],
                     help="right-hand sides (zero/ones: the pass's data-dependent power, not its products)")
@@ -39,6 +41,8 @@ def main():
         sizes = [n] * nb
         M = sum(sizes)
         eng = Engine(sizes, K=1)
+        if a.ld_precision == "f32":   # not called for f64: --lib may name a build without it
+            eng.set_ld_precision(32)
         eng.synth_ld_g(0, 11, a.nsamp, np.zeros(M))
         rs = np.random.RandomState(0)
         for nc in [int(x) for x in a.ncols.split(",")]:
@@ -53,7 +57,9 @@ def main():
                 eng.ld_matvec(0, V)
             t = eng.timers()
             ms = t["ld_ms"] / t["ld_launches"]
-            print(json.dumps(dict(tag=a.tag, shape=shape, ncol=nc, ms_per_pass=round(ms, 4),
+            print(json.dumps(dict(tag=a.tag, shape=shape, ncol=nc, ld_precision=a.ld_precision,
+                                  ms_per_pass=round(ms, 4),
+                                  stored_GB=round(t["ld_bytes"] / t["ld_launches"] / 1e9, 3),
                                   stored_GBs=round(t["ld_bytes"] / t["ld_launches"] / ms / 1e6, 1),
                                   sha=hashlib.sha256(Y.tobytes()).hexdigest()[:16])), flush=True)
         eng.close()
