@@ -35,13 +35,15 @@
 // rotations per row group (fixed order), then over the waves through LDS (wave
 // order).
 // Dcol accumulates over all rows of the strip in registers; every order is fixed.
-#include "common.h"
-
-#include <type_traits>
+//
+// The machinery of one wave -- operand and fragment loads, prefetch ring, tile,
+// MFMA blocks, block reduction, partial stores -- is strip_wave.h's, one
+// definition for the three 4x4x4 kernels here; a kernel's own text is how its
+// waves divide a chunk and where their row sums meet.  k_sym_mfma16 keeps its
+// own loads and ring (see there).
+#include "strip_wave.h"
 
 namespace sgv {
-
-#define MFMA4(a, b, c) __builtin_amdgcn_mfma_f64_4x4x4f64((a), (b), (c), 0, 0, 0)
 
 // Diagnostic build only (make EXTRA=-DSGV_MF_TRACE, tools/strip_trace.py): each
 // workgroup (strip) of the last NC <= 8 MFMA pass records its start / end wall
@@ -63,63 +65,10 @@ __device__ unsigned long long g_mf_trace[3 * MF_TRACE_MAX];
 #define MF_TRACE_END
 #endif
 
-// wave-local LDS ordering point: lanes of one wave exchange data through the
-// tile.  The LDS executes a wave's DS instructions in order, so the write ->
-// read (and read -> next write) order only has to survive compilation: a
-// wavefront-scope fence, which emits no wait (an inline-asm lgkmcnt(0) would
-// make the compiler drain vmcnt as well, stalling on the prefetched loads).
-__device__ __forceinline__ void lds_order() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// Stored element type T of the strip kernels' panels (k_sym_mfma, k_sym_mfma16;
-// sgv_set_ld_precision).  A fragment load is two consecutive columns of one row
-// per lane: 16 B of an f64 panel, 8 B of an f32 one, for the same 16 x 32
-// sub-tile in the same step order.  The prefetch ring keeps them as loaded (an
-// f32 ring is half the registers); the step that takes a fragment widens it to
-// f64 (v_cvt_f64_f32, exact) ahead of the LDS tile, and everything from there on
-// -- tile, MFMA chains, row and column partials -- is one text for both types.
-// So every chain of such a float instance (load form 1) sees the operands, in the
-// order, that the double instance sees on the widened matrix: its products are
-// bitwise equal.  The double case is the text as it was (the same code is
-// generated).  Load form 2 (below) is the one an f32 matrix runs by default.
-typedef float f2 __attribute__((ext_vector_type(2)));
-template <class T>
-struct Frag;
-template <>
-struct Frag<double> {
-  typedef d2 raw;
-  static __device__ __forceinline__ d2 widen(d2 v) { return v; }
-};
-template <>
-struct Frag<float> {
-  typedef f2 raw;
-  static __device__ __forceinline__ d2 widen(f2 v) { return d2{(double)v.x, (double)v.y}; }
-};
-// Load form LF = 2 (float panels only): 16 B per lane, a float4 of 4 consecutive
-// columns, one load per 64-column super-step feeding two 32-column steps -- half
-// the load instructions per element.  Sub-step e' of super-step S is step t = 2 S
-// + e', and its pair index p (the lane's place in the fragment, the tile and the
-// column accumulators) stands for chunk columns 64 S + 4 p + 2 e', + 1 instead
-// of 32 t + 2 p, + 1 (frag_col): the row-part operands, the loads and the column
-// stores take their columns from it, nothing else changes.  A row's terms are
-// then added in another fixed order: not bitwise the LF = 1 sums, still a function
-// of the block alone.
-typedef float f4 __attribute__((ext_vector_type(4)));
 // the form an f32 matrix runs: 2, faster than 1 on every line of the A/B (64 x
 // 15,625 -1...-5 % per pass, 8 x 15,625 -3...-9 %: DESIGN.md 4.6,
 // profiles/ld_f32/ldpass_ab.jsonl); 1 stays compiled as the bitwise pin
 constexpr int F32_FORM_DEFAULT = 2;
-template <int LF>
-__device__ __forceinline__ constexpr int frag_col(int t, int p) {
-  return LF == 2 ? 64 * (t >> 1) + 4 * p + 2 * (t & 1) : 32 * t + 2 * p;
-}
-// 32-column steps with a column below nrem (columns left from the wave's first)
-template <int LF>
-__device__ __forceinline__ int steps_upto(int nrem) {
-  return LF == 2 ? 2 * ((nrem + 63) / 64) : (nrem + 31) / 32;
-}
 
 constexpr int MF_CW = 512;   // chunk width (class 1 items)
 constexpr int MF_LDP = 34;   // k_sym_mfma16's staging row pitch (doubles): conflict-free both ways
@@ -131,28 +80,13 @@ constexpr int MF_LDP = 34;   // k_sym_mfma16's staging row pitch (doubles): conf
 // diagonal panel (r0 == c0) is the strip's last; its diagonal block (chunk
 // columns 0..255, waves 0 and 1) must not feed the column sums, so those waves
 // take zero B operands there (exact: R * 0 adds 0).  Row sums are still written
-// per (panel, chunk) item.  Panel descriptors are wave-uniform (SGPRs); the
-// prefetch of the next row group crosses panel boundaries through selects.
+// per (panel, chunk) item.  Panel descriptors are wave-uniform (SGPRs).
 // Each wave keeps its row sums of the whole panel in its own LDS rows
 // (wrow[wave][row][4 NG]); the four waves' values are added, in wave order, once
 // per panel when the item's row partials are written (one barrier pair per
-// panel).  Steps at or past the chunk's last column take no LDS or MFMA work.
-// DEF: a step's row MFMAs are deferred into the next step and interleaved with
-// its column MFMAs, so consecutive MFMAs of one accumulator chain sit 8 issues
-// apart instead of 4 (2 at NG = 1); every chain accumulates in the same order
-// (bitwise the same sums), the row fragments are double-buffered in registers.
-// RAG: some item of the strip stops short of the strip's widest (band plans).
-// PP (NG = 2): Pk in k_pack's PAIRED layout, so a lane's two column groups
-// (columns n4 and 4 + n4) of one Pk row are one 16-B load: half the P-operand
-// load instructions through the texture-address unit per row group
-// SWZ (NG = 2): column-part B operands without the 4x replication over the
-// MFMA blocks: blocks 0-1 take a row group's 4-row sets in the order 0 1 2 3,
-// blocks 2-3 in the order 2 3 0 1 (fragment a of a lane is row set a ^ (bq &
-// 2)), so one Pk load per row group (lane: row set bq) holds every set a block
-// needs and ds_swizzle hands each lane its set for fragment a (swz_quad); the
-// R fragment loads stay whole 128-B lines.  One box, alternating: the north
-// star -0.4...-0.8 % per pass, the 8-block share -1.4 %; at NG = 1 (8-B
-// operands) even to +0.4 %, so not there (profiles/r06/mf_sw_*.jsonl)
+// panel).
+// DEF: the deferred row/column interleave (mfma_step_deferred); RAG, PP, T, LF
+// and the row sets of NG = 2: StripWave.
 template <int NG, int PD, bool RAG = false, bool DEF = false, bool PP = false, class T = double,
           int LF = 1>
 __global__ __launch_bounds__(256, 2) void k_sym_mfma(const SymStrip* __restrict__ strips,
@@ -164,317 +98,81 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma(const SymStrip* __restrict_
   constexpr int NW = 4;            // waves 0 and 1 own the diagonal half of a chunk
   constexpr int WC = MF_CW / NW;   // columns per wave
   constexpr int NT = WC / 32;      // 32-column steps per wave
-  static_assert(PD >= 1 && PD <= NT && NT % PD == 0, "prefetch depth divides the steps");
-  constexpr int RW = 4 * NG;       // row-sum stride of wrow
-  constexpr bool SWZ = NG == 2;
-  constexpr bool W4 = LF == 2;        // 16-B loads of float panels (frag_col)
-  static_assert(!W4 || (sizeof(T) == 4 && PD == 2 && NT % 2 == 0), "LF = 2: float, two super-steps");
-  typedef typename std::conditional<W4, f4, typename Frag<T>::raw>::type RV;   // a fragment as loaded
-  constexpr int RD = W4 ? NT / 2 : PD;   // ring depth (LF = 2: in super-steps, the same bytes)
+  typedef StripWave<NG, PP, T, LF, RAG> SW;
+  constexpr int RW = SW::RW;
   __shared__ __attribute__((aligned(16))) double rowbuf[NW * SYM_H * RW];   // wrow
-  // the per-wave transpose tile: 16 rows x 32 columns, 16-B piece (row r, pair
-  // p) at slot 16 r + (p ^ (r & 3)) -- unpadded (4 KiB, so the 64 KiB of row
-  // sums and the tiles fit two workgroups per CU) and conflict-free both ways:
-  // a write's 16-lane quarter covers one row, a row-fragment read's quarter
-  // (rows 4q + (l & 3), pairs 4((l >> 2) & 3) + (l >> 4)) 16 distinct slots mod 16
-  __shared__ __attribute__((aligned(16))) double stg[NW][16 * 32];
+  __shared__ __attribute__((aligned(16))) double stg[NW][16 * 32];          // the waves' tiles
   const SymStrip sp = strips[blockIdx.x];
   if (run && !ldg(run)) return;   // no-op pass (pipelined CG past its stop test)
   MF_TRACE_BEGIN
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-  const int lo = lane & 15, hi = lane >> 4, bq = (lane >> 2) & 3, n4 = lane & 3;
-  const int pc = hi + 4 * bq;                          // this lane's column pair in a fragment
   SymItem cur = sitems[sp.it0];
-  const int c0 = cur.c0, ncc = sp.ncmax;               // the strip's chunk, widest item
-  const int PKS = pks;             // Pk row stride (k_pack): 4 NG
-  const double* pkb = pk + (int64_t)cur.voff * PKS;   // Pk of this block (block-relative index)
-  const int cw0 = wid * WC;                            // first chunk column of this wave
-  const bool dhalf = cw0 < SYM_H;                      // wave inside a diagonal panel's diag block
-  // A wave's 32-column steps at or past the chunk's last column (the
-  // ragged last chunk of a panel: 4 % of the north star's steps) take no LDS or
-  // MFMA work -- their row-part B operands are 0 and their column sums are never
-  // read, so every kept sum is bitwise the same; nor do the column MFMAs of the
-  // diagonal-block waves of a diagonal panel (B = 0 there).  The loads stay, so
-  // the load count is the same on every path.
-  const int nta = W4 ? min(NT, max(0, steps_upto<LF>(ncc - cw0)))
-                     : min(NT, max(0, (ncc - cw0 + 31) / 32));
+  const int cw0 = wid * WC;
+  const SW sw(lane, pk + (int64_t)cur.voff * pks, pks, cur.c0, sp.ncmax, cw0, cw0 < SYM_H);
+  const int nta = min(NT, sw.steps_to(sw.ncc));
   double* sb = stg[wid];
-
-  // row-part B operands: P at this wave's columns, reused by every row group
-  static_assert(!PP || NG == 2, "paired Pk rows: two column groups");
-  // one Pk row's values of this lane: column 4 q + n4 for each group q
-  auto ld_prow = [&](int64_t row, double* v) {
-    if constexpr (PP) {
-      const d2 x = ldg((const d2*)(pkb + row * PKS + 2 * n4));
-      v[0] = x.x;
-      v[1] = x.y;
-    } else {
-#pragma unroll
-      for (int q = 0; q < NG; ++q) v[q] = ldg(pkb + row * PKS + 4 * q + n4);
-    }
-  };
   double brow[NT][2][NG];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int col = W4 ? cw0 + frag_col<LF>(t, pc) + e : cw0 + 32 * t + 2 * pc + e;
-      double v[NG];
-      ld_prow(c0 + (col < ncc ? col : 0), v);
-#pragma unroll
-      for (int q = 0; q < NG; ++q) brow[t][e][q] = col < ncc ? v[q] : 0.0;
-    }
+  sw.load_brow(brow);
   double dcol[NT][2][NG];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-#pragma unroll
-      for (int q = 0; q < NG; ++q) dcol[t][e][q] = 0.0;
+  zero(dcol);
 
-  // fragment loads of step (g, t) of a panel (b0 = its element (r0, c0)), 16 B
-  // per lane (8 B of an f32 panel; strides and offsets in elements), branch-free: a row past H clamps (its P is 0), a column past the
-  // chunk loads column 0 (finite; it meets a zero B in the row part and is never
-  // read from the column part).  The base is an opaque integer: a pointer select
-  // is turned back into a branch with one load per side.  Past the strip's last
-  // row group the caller passes the cache-resident Pk with stride 0 (a dummy
-  // fetch: the load count is the same on every path, so the compiler never
-  // drains vmcnt(0) at a branch join or the row-group loop head).
-  // (LF = 2: t counts super-steps, one float4 of columns 64 t + 4 lo ..)
-  auto load_cf = [&](uint64_t b0, int64_t ws, int H, int nci, int g, int t, RV* cf) {
-    asm volatile("" : "+s"(b0));
-    const int xc = W4 ? cw0 + 64 * t + 4 * lo : cw0 + 32 * t + 2 * lo;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int rB = 16 * g + 4 * (SWZ ? a ^ (bq & 2) : a) + hi;
-      const T* row = (const T*)b0 + (int64_t)(rB < H ? rB : H - 1) * ws;
-      cf[a] = ldg_nt((const RV*)(row + (xc < (RAG ? nci : ncc) ? xc : 0)));
-    }
-  };
-  // column-part B operands of row group g of a panel (first row r0): P at its
-  // rows; zero past H and, for the diagonal panel, in the diagonal-block waves
-  // (SWZ: bc[0] = this lane's row set bq, handed to the fragments by swz_quad)
-  auto load_bcol = [&](int r0, int H, bool zero, int g, double (*bc)[NG]) {
-#pragma unroll
-    for (int a = 0; a < (SWZ ? 1 : 4); ++a) {
-      const int rB = 16 * g + 4 * (SWZ ? bq : a) + hi;
-      double v[NG];
-      ld_prow(r0 + (rB < H ? rB : 0), v);
-#pragma unroll
-      for (int q = 0; q < NG; ++q) bc[a][q] = (rB < H && !zero) ? v[q] : 0.0;
-    }
-  };
-  auto pbase = [&](const SymItem& x) { return (uint64_t)((const T*)x.P + (x.c0 - x.r0)); };
-  // a band panel's item narrower than the strip: its columns past nci (never
-  // loaded: the loads above took column 0) read as zero
-  auto band_zero = [&](int nci, int t, d2* cf) {
-    const int xc = W4 ? cw0 + frag_col<LF>(t, lo) : cw0 + 32 * t + 2 * lo;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      cf[a].x = xc < nci ? cf[a].x : 0.0;
-      cf[a].y = xc + 1 < nci ? cf[a].y : 0.0;
-    }
-  };
-
-  uint64_t curb = pbase(cur);
-  // ring of PD steps in flight per wave
-  RV cfq[RD][4];
-  double bcn[SWZ ? 1 : 4][NG];
-#pragma unroll
-  for (int p = 0; p < RD; ++p) load_cf(curb, cur.w, cur.H, cur.nc, 0, p, cfq[p]);
-  load_bcol(cur.r0, cur.H, dhalf && cur.r0 == c0, 0, bcn);
+  uint64_t curb = SW::pbase(cur);
+  FragRing<SW, PD, NT> ring;
+  double bcn[SW::NB][NG];
+  ring.prime(sw, curb, cur);
+  sw.load_bcol(cur.r0, cur.H, sw.col_zero(cur.r0), 0, bcn);
 
 #pragma unroll 1
   for (int s = 0; s < sp.npan; ++s) {                  // uniform over the workgroup
     const bool more = s + 1 < sp.npan;
     const SymItem nx = sitems[sp.it0 + (more ? s + 1 : s)];
-    const uint64_t nxb = more ? pbase(nx) : (uint64_t)pkb;
+    const uint64_t nxb = more ? SW::pbase(nx) : (uint64_t)sw.pkb;
     const int ng = (cur.H + 15) / 16;
 #pragma unroll 1
     for (int g = 0; g < ng; ++g) {
-      // the next row group: this panel's g + 1, or the next panel's first
-      const bool same = g + 1 < ng;
-      const uint64_t gb = same ? curb : nxb;
-      const int64_t gw = same ? cur.w : (more ? nx.w : 0);
-      const int gH = same ? cur.H : (more ? nx.H : 1);
-      const int gnc = same ? cur.nc : nx.nc;
-      const int gn = same ? g + 1 : 0;
-      const int gr0 = same ? cur.r0 : nx.r0;
-      const bool gz = dhalf && gr0 == c0;
+      const NextGroup nxt = sw.next_group(g, ng, cur, curb, more, nx, nxb);
       double bcol[4][NG];
-      // fragment a's set a ^ (bq & 2) from the lane of quad a ^ (bq & 2) of
-      // this 16-lane row
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int q = 0; q < NG; ++q) bcol[a][q] = SWZ ? swz_quad(bcn[0][q], a) : bcn[SWZ ? 0 : a][q];
+      sw.hand_bcol(bcn, bcol);
       double drow[4][NG];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int q = 0; q < NG; ++q) drow[r][q] = 0.0;
-      const bool colz = dhalf && cur.r0 == c0;   // this panel's column B operands are 0
+      zero(drow);
+      const bool colz = sw.col_zero(cur.r0);   // this panel's column B operands are 0
       // a band item narrower than its strip (its panel's last 256 columns): a
       // step wholly past its stored end adds only zeros -- skipped like the
       // steps past the chunk; per panel, so the deferred row MFMAs (DEF) know
       // the item's last active step
-      const int ntp = RAG ? min(nta, max(0, W4 ? steps_upto<LF>(cur.nc - cw0) : (cur.nc - cw0 + 31) / 32)) : nta;
-      d2 cfw[W4 ? 2 : 1][4];                             // LF = 2: a super-step's two steps, widened
+      const int ntp = RAG ? min(nta, sw.steps_to(cur.nc)) : nta;
       d2 rfb[DEF ? 2 : 1][4];                            // row fragments (DEF: this and the previous step)
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         d2 cf[4];
         d2* rf = rfb[DEF ? (t & 1) : 0];
-        const int slot = t % PD;                       // compile-time after unrolling
-        if constexpr (W4) {
-          // a super-step's float4s are taken (and widened) at its first step, and
-          // the same super-step of the next row group goes out in their place
-          if ((t & 1) == 0) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-              const f4 v = cfq[t >> 1][a];
-              cfw[0][a] = d2{(double)v.x, (double)v.y};
-              cfw[1][a] = d2{(double)v.z, (double)v.w};
-            }
-            load_cf(gb, gw, gH, gnc, gn, t >> 1, cfq[t >> 1]);
-            if (t + PD == NT) load_bcol(gr0, gH, gz, gn, bcn);
-          }
-#pragma unroll
-          for (int a = 0; a < 4; ++a) cf[a] = cfw[t & 1][a];
-        } else {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) cf[a] = Frag<T>::widen(cfq[slot][a]);
-        // step + PD goes out here, ahead of this step's LDS and MFMA work
-        if (t + PD < NT) {
-          load_cf(curb, cur.w, cur.H, cur.nc, g, t + PD, cfq[slot]);
-        } else {
-          load_cf(gb, gw, gH, gnc, gn, t + PD - NT, cfq[slot]);
-          if (t + PD == NT) load_bcol(gr0, gH, gz, gn, bcn);
-        }
-        }
+        ring.step(sw, t, g, curb, cur, nxt, bcn, cf);
         if (t >= ntp) continue;                        // wave-uniform: past the chunk / item
-        if (RAG && cur.nc < ncc) band_zero(cur.nc, t, cf);   // uniform: a band item's stored end
-        lds_order();                                   // previous step's tile reads issued
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-          *(d2*)(sb + 32 * (4 * (SWZ ? a ^ (bq & 2) : a) + hi) + 2 * (lo ^ hi)) = cf[a];
-        lds_order();                                   // tile written
-        // the row fragment reads go out right behind the writes (a wave's DS
-        // operations execute in order); the column MFMAs cover their latency
-#pragma unroll
-        for (int r = 0; r < 4; ++r) rf[r] = *(const d2*)(sb + 32 * (4 * r + n4) + 2 * (pc ^ n4));
+        if (RAG && cur.nc < sw.ncc) sw.band_zero(cur.nc, t, cf);   // uniform: a band item's stored end
+        sw.tile_exchange(sb, cf, rf);
         // the MFMA burst at raised wave priority: the SIMD's other wave, whose
         // loads are in flight, takes the issue slots back when this one drains
         // (NC = 4/8 0.7-1.5 % faster per pass on two boxes; NC = 16 1 % slower,
         // not used there -- profiles/r02s10_prio_ab.txt)
         __builtin_amdgcn_s_setprio(1);
-        // x halves of all 4*NG row chains, then the y halves: a chain's two MFMAs
-        // are 4*NG issues apart instead of back to back (same per-chain order)
-        auto row_mfma = [&](const d2* f, int tt) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int q = 0; q < NG; ++q) drow[r][q] = MFMA4(f[r].x, brow[tt][0][q], drow[r][q]);
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int q = 0; q < NG; ++q) drow[r][q] = MFMA4(f[r].y, brow[tt][1][q], drow[r][q]);
-        };
-        if constexpr (DEF) {
-          // column level a of this step, then a quarter of the previous step's
-          // row MFMAs (x halves of rows 2(a&1), +1 for a < 2, then the y halves)
-          const d2* rp = rfb[(t + 1) & 1];
-#pragma unroll
-          for (int a = 0; a < 4; ++a) {
-            if (!colz) {
-#pragma unroll
-              for (int q = 0; q < NG; ++q) {
-                dcol[t][0][q] = MFMA4(cf[a].x, bcol[a][q], dcol[t][0][q]);
-                dcol[t][1][q] = MFMA4(cf[a].y, bcol[a][q], dcol[t][1][q]);
-              }
-            }
-            if (t > 0) {
-              const int tp = t > 0 ? t - 1 : 0;
-#pragma unroll
-              for (int r = 2 * (a & 1); r < 2 * (a & 1) + 2; ++r)
-#pragma unroll
-                for (int q = 0; q < NG; ++q)
-                  drow[r][q] = MFMA4(a < 2 ? rp[r].x : rp[r].y, brow[tp][a < 2 ? 0 : 1][q], drow[r][q]);
-            }
-          }
-          // the row group's last active step: its own row MFMAs now
-          if (t == NT - 1 || t + 1 == ntp) row_mfma(rf, t);
-        } else {
-          if (!colz) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-              for (int q = 0; q < NG; ++q) {
-                dcol[t][0][q] = MFMA4(cf[a].x, bcol[a][q], dcol[t][0][q]);
-                dcol[t][1][q] = MFMA4(cf[a].y, bcol[a][q], dcol[t][1][q]);
-              }
-          }
-          row_mfma(rf, t);
-        }
+        if constexpr (DEF)
+          mfma_step_deferred<NG, NT>(t, t == NT - 1 || t + 1 == ntp, colz, cf, rf,
+                                     rfb[(t + 1) & 1], bcol, brow, dcol[t], drow);
+        else
+          mfma_step<NG>(colz, cf, rf, true, bcol, brow[t], dcol[t], drow);
         __builtin_amdgcn_s_setprio(0);
       }
-      // row sums: the 4 blocks (lanes differing in bits 2,3; DPP row rotations),
-      // kept per wave for the panel
-      double* wb = rowbuf + (wid * SYM_H + 16 * g) * RW;
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-          double v = drow[r][q];
-          v = v + row_ror<12>(v);
-          v = v + row_ror<8>(v);
-          if (bq == 0) wb[(4 * r + hi) * RW + 4 * q + n4] = v;   // D row 4r + m (m = hi)
-        }
+      sw.reduce_blocks(drow, rowbuf + (wid * SYM_H + 16 * g) * RW);   // kept per wave for the panel
     }
-    {   // the item's H x ncol row sums: waves in order, contiguous in rowpart
-      __syncthreads();
-      const int n = cur.H * ncol;
-      double* dst = rowpart + (int64_t)cur.item * SYM_H * ncol;
-      for (int i = threadIdx.x; 2 * i < n; i += NW * 64) {
-        double v[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const int k = 2 * i + e < n ? 2 * i + e : 2 * i;
-          const int row = k / ncol, cc = k - row * ncol;
-          const double* src = rowbuf + row * RW + cc;
-          double x = src[0];
-#pragma unroll
-          for (int w = 1; w < NW; ++w) x += src[w * SYM_H * RW];
-          v[e] = x;
-        }
-        if (2 * i + 1 < n)
-          *(d2*)(dst + 2 * i) = d2{v[0], v[1]};
-        else
-          dst[2 * i] = v[0];
-      }
-      __syncthreads();    // the waves' rows are read before the next panel writes them
-    }
+    __syncthreads();
+    panel_rows_out<NW, NW * 64, RW>(rowbuf, cur.H, ncol, rowpart + (int64_t)cur.item * SYM_H * ncol);
+    __syncthreads();    // the waves' rows are read before the next panel writes them
     cur = nx;
     curb = nxb;
   }
-
-  // column sums over the strip's panels: D_b[m][n] at lane 16m + 4b + n holds
-  // column pair 4b + m = pc, column c = 4q + n.  Whole slot, 16-B stores
-  // (columns the finalize never reads: don't care).
-#pragma unroll
-  for (int q = 0; q < NG; ++q) {
-    const int cc = 4 * q + n4;
-    if (cc < ncol) {
-      double* out = colpart + ((int64_t)sp.slot * ncol + cc) * MF_CW;
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-        if constexpr (W4)
-          *(d2*)(out + cw0 + frag_col<LF>(t, pc)) = d2{dcol[t][0][q], dcol[t][1][q]};
-        else
-          *(d2*)(out + cw0 + 32 * t + 2 * pc) = d2{dcol[t][0][q], dcol[t][1][q]};
-    }
-  }
+  sw.template store_colpart<NT, MF_CW>(colpart + ((int64_t)sp.slot * ncol + sw.n4) * MF_CW + cw0,
+                                       sw.pc, ncol, dcol);
   MF_TRACE_END
 }
 
@@ -512,9 +210,8 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_pair(const SymStrip* __rest
   constexpr int NW = 8;
   constexpr int WC = 64;           // columns per wave
   constexpr int NT = WC / 32;      // 32-column steps per wave
-  static_assert(PD >= 1 && PD <= NT && NT % PD == 0, "prefetch depth divides the steps");
-  constexpr int RW = 4 * NG;
-  constexpr bool SWZ = NG == 2;   // k_sym_mfma's row sets
+  typedef StripWave<NG, PP> SW;
+  constexpr int RW = SW::RW;
   __shared__ __attribute__((aligned(16))) double wrow[4 * SYM_H * RW];   // [segment][row][4 NG]
   constexpr int HS = 3;                                                    // hand-off slots
   __shared__ __attribute__((aligned(16))) double hand[HS][4][4 * NG][WAVE];   // [gg % HS][segment][r, q][lane]
@@ -526,159 +223,56 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_pair(const SymStrip* __rest
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
   const int seg = wid & 3;                               // 128-column segment
   const int h = wid >> 2;                                // half
-  const int lo = lane & 15, hi = lane >> 4, bq = (lane >> 2) & 3, n4 = lane & 3;
-  const int pc = hi + 4 * bq;
   SymItem cur = sitems[sp.it0];
-  const int c0 = cur.c0, ncc = sp.ncmax;
-  const int PKS = pks;
-  const double* pkb = pk + (int64_t)cur.voff * PKS;
-  const int cw0 = seg * 128 + h * WC;                    // first chunk column of this wave
-  const bool dhalf = seg * 128 < SYM_H;                  // the 4-wave kernel's wave `seg`
+  const int cw0 = seg * 128 + h * WC;
+  // dhalf: the 4-wave kernel's wave `seg`
+  const SW sw(lane, pk + (int64_t)cur.voff * pks, pks, cur.c0, sp.ncmax, cw0, seg * 128 < SYM_H);
   // the segment's active 32-column steps (the 4-wave kernel's nta), this wave's share
-  const int nta_seg = min(4, max(0, (ncc - seg * 128 + 31) / 32));
+  const int nta_seg = min(4, max(0, (sw.ncc - seg * 128 + 31) / 32));
   const int nta = min(NT, max(0, nta_seg - NT * h));
   double* sb = stg[wid];
-
-  static_assert(!PP || NG == 2, "paired Pk rows: two column groups");
-  auto ld_prow = [&](int64_t row, double* v) {   // as k_sym_mfma's
-    if constexpr (PP) {
-      const d2 x = ldg((const d2*)(pkb + row * PKS + 2 * n4));
-      v[0] = x.x;
-      v[1] = x.y;
-    } else {
-#pragma unroll
-      for (int q = 0; q < NG; ++q) v[q] = ldg(pkb + row * PKS + 4 * q + n4);
-    }
-  };
   double brow[NT][2][NG];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int col = cw0 + 32 * t + 2 * pc + e;
-      double v[NG];
-      ld_prow(c0 + (col < ncc ? col : 0), v);
-#pragma unroll
-      for (int q = 0; q < NG; ++q) brow[t][e][q] = col < ncc ? v[q] : 0.0;
-    }
+  sw.load_brow(brow);
   double dcol[NT][2][NG];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-#pragma unroll
-      for (int q = 0; q < NG; ++q) dcol[t][e][q] = 0.0;
+  zero(dcol);
 
-  auto load_cf = [&](uint64_t b0, int64_t ws, int H, int g, int t, d2* cf) {
-    asm volatile("" : "+s"(b0));
-    const int xc = cw0 + 32 * t + 2 * lo;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int rB = 16 * g + 4 * (SWZ ? a ^ (bq & 2) : a) + hi;
-      const double* row = (const double*)b0 + (int64_t)(rB < H ? rB : H - 1) * ws;
-      cf[a] = ldg_nt((const d2*)(row + (xc < ncc ? xc : 0)));
-    }
-  };
-  auto load_bcol = [&](int r0, int H, bool zero, int g, double (*bc)[NG]) {
-#pragma unroll
-    for (int a = 0; a < (SWZ ? 1 : 4); ++a) {
-      const int rB = 16 * g + 4 * (SWZ ? bq : a) + hi;
-      double v[NG];
-      ld_prow(r0 + (rB < H ? rB : 0), v);
-#pragma unroll
-      for (int q = 0; q < NG; ++q) bc[a][q] = (rB < H && !zero) ? v[q] : 0.0;
-    }
-  };
-  auto pbase = [&](const SymItem& x) { return (uint64_t)((const double*)x.P + (x.c0 - x.r0)); };
-
-  uint64_t curb = pbase(cur);
-  d2 cfq[PD][4];
-  double bcn[SWZ ? 1 : 4][NG];
-#pragma unroll
-  for (int p = 0; p < PD; ++p) load_cf(curb, cur.w, cur.H, 0, p, cfq[p]);
-  load_bcol(cur.r0, cur.H, dhalf && cur.r0 == c0, 0, bcn);
+  uint64_t curb = SW::pbase(cur);
+  FragRing<SW, PD, NT> ring;
+  double bcn[SW::NB][NG];
+  ring.prime(sw, curb, cur);
+  sw.load_bcol(cur.r0, cur.H, sw.col_zero(cur.r0), 0, bcn);
   if (threadIdx.x < 4) hready[threadIdx.x] = hdone[threadIdx.x] = 0;
   __syncthreads();
-  auto lds_wait_ge = [&](int* ctr, int v) {
-    while (__hip_atomic_load(ctr, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < v)
-      __builtin_amdgcn_s_sleep(1);
-  };
 
   int gg = 0;
 #pragma unroll 1
   for (int s = 0; s < sp.npan; ++s) {
     const bool more = s + 1 < sp.npan;
     const SymItem nx = sitems[sp.it0 + (more ? s + 1 : s)];
-    const uint64_t nxb = more ? pbase(nx) : (uint64_t)pkb;
+    const uint64_t nxb = more ? SW::pbase(nx) : (uint64_t)sw.pkb;
     const int ng = (cur.H + 15) / 16;
 #pragma unroll 1
     for (int g = 0; g < ng; ++g, ++gg) {
-      const bool same = g + 1 < ng;
-      const uint64_t gb = same ? curb : nxb;
-      const int64_t gw = same ? cur.w : (more ? nx.w : 0);
-      const int gH = same ? cur.H : (more ? nx.H : 1);
-      const int gn = same ? g + 1 : 0;
-      const int gr0 = same ? cur.r0 : nx.r0;
-      const bool gz = dhalf && gr0 == c0;
+      const NextGroup nxt = sw.next_group(g, ng, cur, curb, more, nx, nxb);
       double bcol[4][NG];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int q = 0; q < NG; ++q) bcol[a][q] = SWZ ? swz_quad(bcn[0][q], a) : bcn[SWZ ? 0 : a][q];
+      sw.hand_bcol(bcn, bcol);
       double drow[4][NG];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int q = 0; q < NG; ++q) drow[r][q] = 0.0;
-      const bool colz = dhalf && cur.r0 == c0;
+      zero(drow);
+      const bool colz = sw.col_zero(cur.r0);
       d2 rfs[NT][4];                                     // h = 1: row fragments, used after the hand-off
-      auto row_mfma = [&](const d2* f, int tt) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int q = 0; q < NG; ++q) drow[r][q] = MFMA4(f[r].x, brow[tt][0][q], drow[r][q]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int q = 0; q < NG; ++q) drow[r][q] = MFMA4(f[r].y, brow[tt][1][q], drow[r][q]);
-      };
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         d2 cf[4];
-        const int slot = t % PD;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) cf[a] = cfq[slot][a];
-        if (t + PD < NT) {
-          load_cf(curb, cur.w, cur.H, g, t + PD, cfq[slot]);
-        } else {
-          load_cf(gb, gw, gH, gn, t + PD - NT, cfq[slot]);
-          if (t + PD == NT) load_bcol(gr0, gH, gz, gn, bcn);
-        }
+        ring.step(sw, t, g, curb, cur, nxt, bcn, cf);
         if (t >= nta) continue;
-        d2* rf = rfs[t];
-        lds_order();
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-          *(d2*)(sb + 32 * (4 * (SWZ ? a ^ (bq & 2) : a) + hi) + 2 * (lo ^ hi)) = cf[a];
-        lds_order();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) rf[r] = *(const d2*)(sb + 32 * (4 * r + n4) + 2 * (pc ^ n4));
+        sw.tile_exchange(sb, cf, rfs[t]);
         __builtin_amdgcn_s_setprio(1);
-        if (!colz) {
-#pragma unroll
-          for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int q = 0; q < NG; ++q) {
-              dcol[t][0][q] = MFMA4(cf[a].x, bcol[a][q], dcol[t][0][q]);
-              dcol[t][1][q] = MFMA4(cf[a].y, bcol[a][q], dcol[t][1][q]);
-            }
-        }
-        if (h == 0) row_mfma(rf, t);                     // the chain's first half
+        mfma_step<NG>(colz, cf, rfs[t], h == 0, bcol, brow[t], dcol[t], drow);   // h = 0: the chain's first half
         __builtin_amdgcn_s_setprio(0);
       }
       double* hs = &hand[gg % HS][seg][0][0];
       if (h == 0) {
-        lds_wait_ge(&hdone[seg], gg - HS + 1);   // slot gg % HS taken back
+        lds_wait_ge<__ATOMIC_ACQUIRE>(&hdone[seg], gg - HS + 1);   // slot gg % HS taken back
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -686,7 +280,7 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_pair(const SymStrip* __rest
         __hip_atomic_store(&hready[seg], gg + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
       if (h == 1) {
-        lds_wait_ge(&hready[seg], gg + 1);
+        lds_wait_ge<__ATOMIC_ACQUIRE>(&hready[seg], gg + 1);
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -695,56 +289,19 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_pair(const SymStrip* __rest
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int t = 0; t < NT; ++t)
-          if (t < nta) row_mfma(rfs[t], t);             // the chain's second half
+          if (t < nta) row_mfma<NG>(rfs[t], brow[t], drow);   // the chain's second half
         __builtin_amdgcn_s_setprio(0);
-        double* wb = wrow + (seg * SYM_H + 16 * g) * RW;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int q = 0; q < NG; ++q) {
-            double v = drow[r][q];
-            v = v + row_ror<12>(v);
-            v = v + row_ror<8>(v);
-            if (bq == 0) wb[(4 * r + hi) * RW + 4 * q + n4] = v;
-          }
+        sw.reduce_blocks(drow, wrow + (seg * SYM_H + 16 * g) * RW);
       }
     }
-    {   // the item's H x ncol row sums: segments in order, contiguous in rowpart
-      __syncthreads();
-      const int n = cur.H * ncol;
-      double* dst = rowpart + (int64_t)cur.item * SYM_H * ncol;
-      for (int i = threadIdx.x; 2 * i < n; i += NW * 64) {
-        double v[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const int k = 2 * i + e < n ? 2 * i + e : 2 * i;
-          const int row = k / ncol, cc = k - row * ncol;
-          const double* src = wrow + row * RW + cc;
-          double x = src[0];
-#pragma unroll
-          for (int w = 1; w < 4; ++w) x += src[w * SYM_H * RW];
-          v[e] = x;
-        }
-        if (2 * i + 1 < n)
-          *(d2*)(dst + 2 * i) = d2{v[0], v[1]};
-        else
-          dst[2 * i] = v[0];
-      }
-      __syncthreads();
-    }
+    __syncthreads();   // the item's row sums: segments in order
+    panel_rows_out<4, NW * 64, RW>(wrow, cur.H, ncol, rowpart + (int64_t)cur.item * SYM_H * ncol);
+    __syncthreads();
     cur = nx;
     curb = nxb;
   }
-#pragma unroll
-  for (int q = 0; q < NG; ++q) {
-    const int cc = 4 * q + n4;
-    if (cc < ncol) {
-      double* out = colpart + ((int64_t)sp.slot * ncol + cc) * MF_CW;
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-        *(d2*)(out + cw0 + 32 * t + 2 * pc) = d2{dcol[t][0][q], dcol[t][1][q]};
-    }
-  }
+  sw.template store_colpart<NT, MF_CW>(colpart + ((int64_t)sp.slot * ncol + sw.n4) * MF_CW + cw0,
+                                       sw.pc, ncol, dcol);
 }
 
 // Wide strips (dense-triangle blocks, 3-8 columns): one 8-wave workgroup per
@@ -777,9 +334,8 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_wide(const SymStrip* __rest
   constexpr int NW = 8;
   constexpr int WC = MFW_CW / NW;  // columns per wave
   constexpr int NT = WC / 32;      // 32-column steps per wave
-  static_assert(PD >= 1 && PD <= NT && NT % PD == 0, "prefetch depth divides the steps");
-  constexpr int RW = 4 * NG;
-  constexpr bool SWZ = NG == 2;    // k_sym_mfma's row sets
+  typedef StripWave<NG, PP> SW;
+  constexpr int RW = SW::RW;
   __shared__ __attribute__((aligned(16))) double hand[MFW_RD][NW][16 * RW];
   __shared__ int hready[MFW_RD], hdone[MFW_RD];   // writes into / combines of each buffer
   __shared__ __attribute__((aligned(16))) double stg[NW][16 * 32];
@@ -787,185 +343,64 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_wide(const SymStrip* __rest
   if (run && !ldg(run)) return;
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-  const int lo = lane & 15, hi = lane >> 4, bq = (lane >> 2) & 3, n4 = lane & 3;
-  const int pc = hi + 4 * bq;
   SymItem cur = sitems[sp.it0];
-  const int c0 = cur.c0, ncc = sp.ncmax;
   constexpr int PKS = 4 * NG;      // Pk row stride (k_pack)
-  const double* pkb = pk + (int64_t)cur.voff * PKS;
   const int cw0 = wid * WC;
-  const bool dhalf = cw0 < SYM_H;                      // waves 0 and 1: the diagonal block
-  const int nta = min(NT, max(0, (ncc - cw0 + 31) / 32));
+  // dhalf: waves 0 and 1, the diagonal block
+  const SW sw(lane, pk + (int64_t)cur.voff * PKS, PKS, cur.c0, sp.ncmax, cw0, cw0 < SYM_H);
+  const int nta = min(NT, sw.steps_to(sw.ncc));
   // waves with columns inside the strip
-  const int nact = idle ? min(NW, (ncc + WC - 1) / WC) : NW;
+  const int nact = idle ? min(NW, (sw.ncc + WC - 1) / WC) : NW;
   if (threadIdx.x < MFW_RD) hready[threadIdx.x] = hdone[threadIdx.x] = 0;
   __syncthreads();
   if (wid >= nact) return;
   double* sb = stg[wid];
-  auto lds_wait_ge = [](int* ctr, int v) {
-    while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < v)
-      __builtin_amdgcn_s_sleep(1);
-  };
-
-  static_assert(!PP || NG == 2, "paired Pk rows: two column groups");
-  auto ld_prow = [&](int64_t row, double* v) {   // as k_sym_mfma's
-    if constexpr (PP) {
-      const d2 x = ldg((const d2*)(pkb + row * PKS + 2 * n4));
-      v[0] = x.x;
-      v[1] = x.y;
-    } else {
-#pragma unroll
-      for (int q = 0; q < NG; ++q) v[q] = ldg(pkb + row * PKS + 4 * q + n4);
-    }
-  };
   double brow[NT][2][NG];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int col = cw0 + 32 * t + 2 * pc + e;
-      double v[NG];
-      ld_prow(c0 + (col < ncc ? col : 0), v);
-#pragma unroll
-      for (int q = 0; q < NG; ++q) brow[t][e][q] = col < ncc ? v[q] : 0.0;
-    }
+  sw.load_brow(brow);
   double dcol[NT][2][NG];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-#pragma unroll
-      for (int q = 0; q < NG; ++q) dcol[t][e][q] = 0.0;
+  zero(dcol);
 
-  auto load_cf = [&](uint64_t b0, int64_t ws, int H, int g, int t, d2* cf) {
-    asm volatile("" : "+s"(b0));
-    const int xc = cw0 + 32 * t + 2 * lo;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int rB = 16 * g + 4 * (SWZ ? a ^ (bq & 2) : a) + hi;
-      const double* row = (const double*)b0 + (int64_t)(rB < H ? rB : H - 1) * ws;
-      cf[a] = ldg_nt((const d2*)(row + (xc < ncc ? xc : 0)));
-    }
-  };
-  auto load_bcol = [&](int r0, int H, bool zero, int g, double (*bc)[NG]) {
-#pragma unroll
-    for (int a = 0; a < (SWZ ? 1 : 4); ++a) {
-      const int rB = 16 * g + 4 * (SWZ ? bq : a) + hi;
-      double v[NG];
-      ld_prow(r0 + (rB < H ? rB : 0), v);
-#pragma unroll
-      for (int q = 0; q < NG; ++q) bc[a][q] = (rB < H && !zero) ? v[q] : 0.0;
-    }
-  };
-  auto pbase = [&](const SymItem& x) { return (uint64_t)((const double*)x.P + (x.c0 - x.r0)); };
-
-  uint64_t curb = pbase(cur);
-  d2 cfq[PD][4];
-  double bcn[SWZ ? 1 : 4][NG];
-#pragma unroll
-  for (int p = 0; p < PD; ++p) load_cf(curb, cur.w, cur.H, 0, p, cfq[p]);
-  load_bcol(cur.r0, cur.H, dhalf && cur.r0 == c0, 0, bcn);
+  uint64_t curb = SW::pbase(cur);
+  FragRing<SW, PD, NT> ring;
+  double bcn[SW::NB][NG];
+  ring.prime(sw, curb, cur);
+  sw.load_bcol(cur.r0, cur.H, sw.col_zero(cur.r0), 0, bcn);
 
   // this lane's place in the strip's colpart slot, kept in vector registers
   // over the loops (the scalar file is full: no spills)
-  double* outp = colpart + ((int64_t)sp.slot * ncol + n4) * MFW_CW + cw0 + 2 * pc;
+  double* outp = colpart + ((int64_t)sp.slot * ncol + sw.n4) * MFW_CW + cw0 + 2 * sw.pc;
   asm volatile("" : "+v"(outp));
   int gg = 0;   // row groups done: buffer gg % MFW_RD, round gg / MFW_RD
 #pragma unroll 1
   for (int s = 0; s < sp.npan; ++s) {                  // uniform over the workgroup
     const bool more = s + 1 < sp.npan;
     const SymItem nx = sitems[sp.it0 + (more ? s + 1 : s)];
-    const uint64_t nxb = more ? pbase(nx) : (uint64_t)pkb;
+    const uint64_t nxb = more ? SW::pbase(nx) : (uint64_t)sw.pkb;
     const int ng = (cur.H + 15) / 16;
 #pragma unroll 1
     for (int g = 0; g < ng; ++g) {
-      const bool same = g + 1 < ng;
-      const uint64_t gb = same ? curb : nxb;
-      const int64_t gw = same ? cur.w : (more ? nx.w : 0);
-      const int gH = same ? cur.H : (more ? nx.H : 1);
-      const int gn = same ? g + 1 : 0;
-      const int gr0 = same ? cur.r0 : nx.r0;
-      const bool gz = dhalf && gr0 == c0;
+      const NextGroup nxt = sw.next_group(g, ng, cur, curb, more, nx, nxb);
       double bcol[4][NG];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int q = 0; q < NG; ++q) bcol[a][q] = SWZ ? swz_quad(bcn[0][q], a) : bcn[SWZ ? 0 : a][q];
+      sw.hand_bcol(bcn, bcol);
       double drow[4][NG];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int q = 0; q < NG; ++q) drow[r][q] = 0.0;
-      const bool colz = dhalf && cur.r0 == c0;   // this panel's column B operands are 0
+      zero(drow);
+      const bool colz = sw.col_zero(cur.r0);   // this panel's column B operands are 0
       d2 rfb[2][4];                               // row fragments: this and the previous step
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         d2 cf[4];
-        d2* rf = rfb[t & 1];
-        const int slot = t % PD;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) cf[a] = cfq[slot][a];
-        if (t + PD < NT) {
-          load_cf(curb, cur.w, cur.H, g, t + PD, cfq[slot]);
-        } else {
-          load_cf(gb, gw, gH, gn, t + PD - NT, cfq[slot]);
-          if (t + PD == NT) load_bcol(gr0, gH, gz, gn, bcn);
-        }
+        ring.step(sw, t, g, curb, cur, nxt, bcn, cf);
         if (t >= nta) continue;                        // wave-uniform: past the chunk
-        lds_order();
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-          *(d2*)(sb + 32 * (4 * (SWZ ? a ^ (bq & 2) : a) + hi) + 2 * (lo ^ hi)) = cf[a];
-        lds_order();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) rf[r] = *(const d2*)(sb + 32 * (4 * r + n4) + 2 * (pc ^ n4));
+        sw.tile_exchange(sb, cf, rfb[t & 1]);
         __builtin_amdgcn_s_setprio(1);
-        // column level a of this step, then a quarter of the previous step's
-        // row MFMAs (k_sym_mfma's DEF order)
-        const d2* rp = rfb[(t + 1) & 1];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          if (!colz) {
-#pragma unroll
-            for (int q = 0; q < NG; ++q) {
-              dcol[t][0][q] = MFMA4(cf[a].x, bcol[a][q], dcol[t][0][q]);
-              dcol[t][1][q] = MFMA4(cf[a].y, bcol[a][q], dcol[t][1][q]);
-            }
-          }
-          if (t > 0) {
-            const int tp = t > 0 ? t - 1 : 0;
-#pragma unroll
-            for (int r = 2 * (a & 1); r < 2 * (a & 1) + 2; ++r)
-#pragma unroll
-              for (int q = 0; q < NG; ++q)
-                drow[r][q] = MFMA4(a < 2 ? rp[r].x : rp[r].y, brow[tp][a < 2 ? 0 : 1][q], drow[r][q]);
-          }
-        }
-        if (t == NT - 1 || t + 1 == nta) {   // the row group's last active step: its own row MFMAs
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int q = 0; q < NG; ++q) drow[r][q] = MFMA4(rf[r].x, brow[t][0][q], drow[r][q]);
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int q = 0; q < NG; ++q) drow[r][q] = MFMA4(rf[r].y, brow[t][1][q], drow[r][q]);
-        }
+        mfma_step_deferred<NG, NT>(t, t == NT - 1 || t + 1 == nta, colz, cf, rfb[t & 1],
+                                   rfb[(t + 1) & 1], bcol, brow, dcol[t], drow);
         __builtin_amdgcn_s_setprio(0);
       }
       // the row group's row sums: 4 blocks (DPP), handed to the combining wave
       const int hs = gg % MFW_RD, gen = gg / MFW_RD;
-      lds_wait_ge(&hdone[hs], gen);                    // buffer hs free (its last round combined)
-      double* rb = hand[hs][wid];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-          double v = drow[r][q];
-          v = v + row_ror<12>(v);
-          v = v + row_ror<8>(v);
-          if (bq == 0) rb[(4 * r + hi) * RW + 4 * q + n4] = v;   // D row 4r + m (m = hi)
-        }
+      lds_wait_ge<__ATOMIC_RELAXED>(&hdone[hs], gen);   // buffer hs free (its last round combined)
+      sw.reduce_blocks(drow, hand[hs][wid]);
       // a wave's DS operations execute in order, so the counter's add lands
       // after the row sums; the fences keep the compiler's order and wait for
       // nothing (the fragments stay in flight)
@@ -974,7 +409,7 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_wide(const SymStrip* __rest
         __hip_atomic_fetch_add(&hready[hs], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       // the panel's row group g is combined by wave g mod 8 (wave 0 for an idle one)
       if (wid == ((g & (NW - 1)) < nact ? (g & (NW - 1)) : 0)) {   // the waves in order
-        lds_wait_ge(&hready[hs], nact * (gen + 1));
+        lds_wait_ge<__ATOMIC_RELAXED>(&hready[hs], nact * (gen + 1));
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         double* dst = rowpart + ((int64_t)cur.item * SYM_H + 16 * g) * ncol;
 #pragma unroll
@@ -1001,16 +436,8 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_wide(const SymStrip* __rest
     cur = nx;
     curb = nxb;
   }
-  // column sums over the strip's panels (whole 128-column segment, 16-B stores)
-#pragma unroll
-  for (int q = 0; q < NG; ++q) {
-    const int cc = 4 * q + n4;
-    if (cc < ncol) {
-      double* out = outp + 4 * q * MFW_CW;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) *(d2*)(out + 32 * t) = d2{dcol[t][0][q], dcol[t][1][q]};
-    }
-  }
+  // outp already holds the lane's pair: p = 0
+  sw.template store_colpart<NT, MFW_CW>(outp, 0, ncol, dcol);
 }
 
 // 13..16 right-hand sides: v_mfma_f64_16x16x4f64 (one 16-column group, 140
@@ -1021,6 +448,15 @@ __global__ __launch_bounds__(512, 1) void k_sym_mfma_wide(const SymStrip* __rest
 //   16x16x4 f64 C/D layout (cdna_hip_programming.md): D[(l>>4) + 4r][l & 15].
 typedef double d4 __attribute__((ext_vector_type(4)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
+// This kernel keeps its own text of the loads, the ring and the next-group
+// selects (StripWave::load_cf / load_bcol / band_zero, FragRing, next_group in
+// strip_wave.h, with one column group across 16 lanes and no row sets): at
+// 252-255 VGPRs its schedule turns on the order of its statements.  On the
+// shared forms the f32 16-B ragged instance went from 255 to 256 VGPRs and the
+// 16-column f32 band pass (M = 1e6, bw = 1,000) from 2.2525 to 2.2874 ms
+// (medians of 5, builds alternating; the parent's spread 0.0133:
+// profiles/strip_refactor/speed_band_f32_rerun5.jsonl); with this text every
+// instance compiles to the instruction stream it had.
 // TB: the row-part B operands of the last TB steps kept in LDS (8 TB doubles per
 // lane, 4 TB KiB per wave, read back per step as 4 x 16 B) instead of registers
 template <int PD, bool RAG = false, int TB = 0, class T = double, int LF = 1>
@@ -1033,7 +469,7 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
   constexpr int LDP = MF_LDP;
   constexpr int MF_WC = MF_CW / 4; // columns per wave
   constexpr int MF_NT = MF_WC / 32;
-  constexpr bool W4 = LF == 2;        // 16-B loads of float panels (frag_col), as k_sym_mfma
+  constexpr bool W4 = LF == 2;        // 16-B loads of float panels (frag_col)
   static_assert(!W4 || (sizeof(T) == 4 && PD == 2 && MF_NT % 2 == 0), "LF = 2: float, two super-steps");
   typedef typename std::conditional<W4, f4, typename Frag<T>::raw>::type RV;   // a fragment as loaded
   constexpr int RD = W4 ? MF_NT / 2 : PD;
@@ -1052,7 +488,7 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
   const int cw0 = wid * MF_WC;                         // first chunk column of this wave
   const bool dhalf = cw0 < SYM_H;
   const int nta = W4 ? min(MF_NT, max(0, steps_upto<LF>(ncc - cw0)))
-                     : min(MF_NT, max(0, (ncc - cw0 + 31) / 32));   // as k_sym_mfma
+                     : min(MF_NT, max(0, (ncc - cw0 + 31) / 32));   // StripWave::steps_to
 
   double* sb = stg[wid];
   // row-part B operands (P at this wave's columns), reused by every row group
@@ -1083,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
       cf[a] = ldg_nt((const RV*)(row + (xc < (RAG ? nci : ncc) ? xc : 0)));
     }
   };
-  auto band_zero = [&](int nci, int t, d2* cf) {   // as k_sym_mfma
+  auto band_zero = [&](int nci, int t, d2* cf) {
     const int xc = W4 ? cw0 + frag_col<LF>(t, lo) : cw0 + 32 * t + 2 * lo;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
@@ -1136,7 +572,7 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
       for (int t = 0; t < MF_NT; ++t) {
         d2 cf[4], rf[4];
         const int slot = t % PD;                       // compile-time after unrolling
-        if constexpr (W4) {   // as k_sym_mfma
+        if constexpr (W4) {
           if ((t & 1) == 0) {
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
@@ -1161,7 +597,7 @@ __global__ __launch_bounds__(256, 2) void k_sym_mfma16(const SymStrip* __restric
         }
         }
         if (t >= nta) continue;
-        if (RAG && cw0 + (W4 ? 64 * (t >> 1) : 32 * t) >= cur.nc) continue;   // as k_sym_mfma
+        if (RAG && cw0 + (W4 ? 64 * (t >> 1) : 32 * t) >= cur.nc) continue;   // wholly past the item
         if (RAG && cur.nc < ncc) band_zero(cur.nc, t, cf);
         lds_order();                                   // previous step's tile reads done
 #pragma unroll
@@ -1411,32 +847,40 @@ static int f32_form() {
   return (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : F32_FORM_DEFAULT;
 }
 
+// The (stored type, load form, ragged) instance of a 4-wave strip kernel a
+// launch takes, chosen once: f(StripInst<T, LF, RAG>{}) launches it.
+template <class T, int LF, bool RAG>
+struct StripInst {
+  typedef T elem;
+  static constexpr int lf = LF;
+  static constexpr bool rag = RAG;
+};
+template <class F>
+static void with_strip_inst(bool f32, bool ragged, F f) {
+  const int form = f32 ? f32_form() : 1;
+  if (form == 2)
+    ragged ? f(StripInst<float, 2, true>{}) : f(StripInst<float, 2, false>{});
+  else if (f32)
+    ragged ? f(StripInst<float, 1, true>{}) : f(StripInst<float, 1, false>{});
+  else
+    ragged ? f(StripInst<double, 1, true>{}) : f(StripInst<double, 1, false>{});
+}
+
 template <int NG, bool PP = false>
 static void launch_mf(const SymStrip* d_strips, int nstrips, const SymItem* d_sitems,
                       const double* d_pk, int nc, double* rowpart, double* colpart,
                       const int* run, int pks, bool ragged, int pair, bool f32, hipStream_t st) {
   // prefetch depth 2 measured best (PD 1/2/4: 11.64/11.16/12.27 ms at NC=4, M=1e6)
-  if (f32 && f32_form() == 2 && ragged)
-    hipLaunchKernelGGL((k_sym_mfma<NG, 2, true, false, PP, float, 2>), dim3(nstrips), dim3(256), 0,
-                       st, d_strips, d_sitems, d_pk, nc, rowpart, colpart, run, pks);
-  else if (f32 && f32_form() == 2)
-    hipLaunchKernelGGL((k_sym_mfma<NG, 2, false, true, PP, float, 2>), dim3(nstrips), dim3(256), 0,
-                       st, d_strips, d_sitems, d_pk, nc, rowpart, colpart, run, pks);
-  else if (f32 && ragged)
-    hipLaunchKernelGGL((k_sym_mfma<NG, 2, true, false, PP, float>), dim3(nstrips), dim3(256), 0,
-                       st, d_strips, d_sitems, d_pk, nc, rowpart, colpart, run, pks);
-  else if (f32)
-    hipLaunchKernelGGL((k_sym_mfma<NG, 2, false, true, PP, float>), dim3(nstrips), dim3(256), 0,
-                       st, d_strips, d_sitems, d_pk, nc, rowpart, colpart, run, pks);
-  else if (ragged)
-    hipLaunchKernelGGL((k_sym_mfma<NG, 2, true, false, PP>), dim3(nstrips), dim3(256), 0, st,
-                       d_strips, d_sitems, d_pk, nc, rowpart, colpart, run, pks);
-  else if (pair >= 1)
+  if (!f32 && !ragged && pair >= 1)
     hipLaunchKernelGGL((k_sym_mfma_pair<NG, 2, PP>), dim3(nstrips), dim3(512), 0, st, d_strips,
                        d_sitems, d_pk, nc, rowpart, colpart, run, pks);
   else
-    hipLaunchKernelGGL((k_sym_mfma<NG, 2, false, true, PP>), dim3(nstrips), dim3(256), 0, st,
-                       d_strips, d_sitems, d_pk, nc, rowpart, colpart, run, pks);
+    with_strip_inst(f32, ragged, [&](auto i) {
+      typedef decltype(i) I;   // RAG for band plans, DEF otherwise
+      hipLaunchKernelGGL((k_sym_mfma<NG, 2, I::rag, !I::rag, PP, typename I::elem, I::lf>),
+                         dim3(nstrips), dim3(256), 0, st, d_strips, d_sitems, d_pk, nc, rowpart,
+                         colpart, run, pks);
+    });
 }
 
 // 5-8-column strip passes read Pk PAIRED (k_pack), in either strip kernel.
@@ -1496,24 +940,12 @@ hipError_t launch_sym_mfma(int nc, const SymStrip* d_strips, int nstrips, const 
       // with 3 / 7 spilled before): band plans the last 2 steps (-0.6 % per
       // 16-column band pass), dense plans the last one (even; 2 steps there +2 %)
       // -- profiles/r06/mf16_bl_*.jsonl, mf16_tb_*.jsonl; products bitwise equal
-      if (f32 && f32_form() == 2 && ragged)
-        hipLaunchKernelGGL((k_sym_mfma16<2, true, 2, float, 2>), dim3(nstrips), dim3(256), 0, st,
-                           d_strips, d_sitems, d_pk, nc, rowpart, colpart, pa.run);
-      else if (f32 && f32_form() == 2)
-        hipLaunchKernelGGL((k_sym_mfma16<2, false, 1, float, 2>), dim3(nstrips), dim3(256), 0, st,
-                           d_strips, d_sitems, d_pk, nc, rowpart, colpart, pa.run);
-      else if (f32 && ragged)
-        hipLaunchKernelGGL((k_sym_mfma16<2, true, 2, float>), dim3(nstrips), dim3(256), 0, st,
-                           d_strips, d_sitems, d_pk, nc, rowpart, colpart, pa.run);
-      else if (f32)
-        hipLaunchKernelGGL((k_sym_mfma16<2, false, 1, float>), dim3(nstrips), dim3(256), 0, st,
-                           d_strips, d_sitems, d_pk, nc, rowpart, colpart, pa.run);
-      else if (ragged)
-        hipLaunchKernelGGL((k_sym_mfma16<2, true, 2>), dim3(nstrips), dim3(256), 0, st, d_strips,
-                           d_sitems, d_pk, nc, rowpart, colpart, pa.run);
-      else
-        hipLaunchKernelGGL((k_sym_mfma16<2, false, 1>), dim3(nstrips), dim3(256), 0, st, d_strips,
-                           d_sitems, d_pk, nc, rowpart, colpart, pa.run);
+      with_strip_inst(f32, ragged, [&](auto i) {
+        typedef decltype(i) I;
+        hipLaunchKernelGGL((k_sym_mfma16<2, I::rag, I::rag ? 2 : 1, typename I::elem, I::lf>),
+                           dim3(nstrips), dim3(256), 0, st, d_strips, d_sitems, d_pk, nc, rowpart,
+                           colpart, pa.run);
+      });
       break;
   }
   return hipGetLastError();

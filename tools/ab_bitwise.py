@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Bitwise A/B of two builds: run fixed LD passes (packed VALU/MFMA, dense, band)
-and full VAMP runs of golden cases through the library at --lib, print one
-SHA-256 per result.  Two builds whose lines are equal produce the same bits.
+"""Bitwise A/B of two builds: run fixed LD passes (packed VALU/MFMA, dense, the
+wide-item block sizes, band; the last two also f32-stored) and full VAMP runs of
+golden cases through the library at --lib, print one SHA-256 per result.  Two
+builds whose lines are equal produce the same bits (under the same SGV_AB
+switches: run it once per arm).
 
   python tools/ab_bitwise.py --lib sgvamp-py_amd/libsgvamp_hip.so > a.txt
   python tools/ab_bitwise.py --lib ab_lib/base.so > b.txt; diff a.txt b.txt"""
@@ -52,14 +54,34 @@ def main():
         for nc in (1, 2, 3, 5, 8, 12, 16):
             print("matvec %s nc=%d %s" % (fmt, nc, h(eng.ld_matvec(0, V[:nc]))))
         eng.close()
+    # the wide-item sizes (tests/test_gpu_wide_items.py): 9-panel column classes
+    # (8 + 1-panel strip pairs), ragged chunk ends on, just past and far before
+    # wave boundaries, a one-marker block; f64 and f32-stored
+    wsizes = [8500, 1281, 513, 257, 1]
+    wblocks = []
+    for n in wsizes:
+        U = np.triu(np.random.RandomState(1000 + n).standard_normal((n, n)) / np.sqrt(n))
+        wblocks.append(U + np.triu(U, 1).T)
+    VW = rs.normal(size=(16, sum(wsizes)))
+    for bits, tag in ((64, "wide"), (32, "wide f32")):
+        eng = Engine(wsizes, K=1)
+        eng.set_ld_precision(bits)
+        eng.set_ridge(0.1)
+        for b, B in enumerate(wblocks):
+            eng.set_ld_block(0, b, B)
+        for nc in (3, 4, 5, 8, 13, 16):
+            print("matvec %s nc=%d %s" % (tag, nc, h(eng.ld_matvec(0, VW[:nc]))))
+        eng.close()
     A = windowed_ld(6000, 700, seed=3, taps=40)
     L = BlockLD.from_csr(A)
-    eng = Engine(L.block_sizes, K=1)
-    L.upload(eng, 0, 0)
     W = rs.normal(size=(16, 6000))
-    for nc in (1, 2, 8, 16):
-        print("matvec band nc=%d %s" % (nc, h(eng.ld_matvec(0, W[:nc]))))
-    eng.close()
+    for bits, tag, ncs in ((64, "band", (1, 2, 8, 16)), (32, "band f32", (1, 2, 4, 8, 16))):
+        eng = Engine(L.block_sizes, K=1)
+        eng.set_ld_precision(bits)
+        L.upload(eng, 0, 0)
+        for nc in ncs:
+            print("matvec %s nc=%d %s" % (tag, nc, h(eng.ld_matvec(0, W[:nc]))))
+        eng.close()
     # many blocks (> 8): the two-launch reduction + control path at one rank
     import hip_backend as hb
     sizes = [300] * 20
