@@ -395,6 +395,22 @@ int sgv_metrics_end(sgv_ctx* ctx, double* out4);
  * scipy cg (src/sgvamp.py:316,332) and R @ x (:352,359). */
 int sgv_ld_matvec(sgv_ctx* ctx, int ld, int ncol, const double* v, double* y);
 
+/* One LD pass over the RAW R of matrix ld (the ridge is NOT applied: the caller
+ * folds it into c1/c2 as the solver does) with the whole fused epilogue:
+ *   out_j  = c1[j] (R in_j) + c2[j] in_j
+ *   yout_j = ys1 (R in_j) + ys0 in_j          for j in yout_mask
+ *   dots[j] = sum_i w_j[i] out_j[i]           for j in dot_mask (the pass's
+ *             partials through the ordered reduction the CG uses)
+ * in, out, yout, w: [ncol][M_local] host, dense; c1, c2, dots: [ncol]; ncol 1..16.
+ * w == NULL with dot_mask != 0: dot_j aliases in_j (the CG's p.q, same pointer).
+ * run: -1 = PassArgs::run null; 0 / 1 = a device word holding that value is
+ * passed as PassArgs::run.  out and yout are uploaded from the caller's buffers
+ * first, so a no-op pass must return them unchanged (dots are unspecified then,
+ * as are the dots of columns outside dot_mask). */
+int sgv_ld_pass_ex(sgv_ctx* ctx, int ld, int ncol, const double* in, const double* c1,
+                   const double* c2, const double* w, uint32_t dot_mask, uint32_t yout_mask,
+                   double ys1, double ys0, int run, double* out, double* yout, double* dots);
+
 /* Batched scipy-1.15.3 CG on (c1 R_s + c2 I) x = b for ncol columns sharing LD
  * `ld` (operator seam con_grad, src/sgvamp.py:7).  x: in = x0, out = solution.
  * iters_out/info_out [ncol]. */

@@ -447,6 +447,7 @@ extern "C" void sgv_destroy(sgv_ctx* c) {
   (void)hipFree(c->d_counts);
   (void)hipFree(c->d_tot);
   (void)hipFree(c->d_pq);
+  if (c->d_runw) (void)hipFree(c->d_runw);
   if (c->h_tot) (void)hipHostFree(c->h_tot);
   if (c->d_cgs) (void)hipFree(c->d_cgs);
   if (c->d_rhonew) (void)hipFree(c->d_rhonew);

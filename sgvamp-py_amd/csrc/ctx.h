@@ -274,6 +274,7 @@ struct sgv_ctx {
   double* d_tot = nullptr;
   double* h_tot = nullptr;
   double* d_pq = nullptr;
+  int* d_runw = nullptr;        // sgv_ld_pass_ex: the device word passed as PassArgs::run
   int nbmax = 0;
   // staging (device) and pinned host staging: every host<->device copy goes
   // through pinned memory and a spin wait (pageable copies block inside the

@@ -1107,6 +1107,53 @@ extern "C" int sgv_ld_matvec(sgv_ctx* c, int ld, int ncol, const double* v, doub
   return SGV_OK;
 }
 
+// One pass with the whole PassArgs, as the CG and gamw learning fill it: the
+// columns in S[0..), out S[MAXC..), yout S[2 MAXC..), dot weights S[3 MAXC..);
+// the partial dots go through ld_parts + reduce_dev into d_pq like cg_loop's.
+extern "C" int sgv_ld_pass_ex(sgv_ctx* c, int ld, int ncol, const double* in, const double* c1,
+                              const double* c2, const double* w, uint32_t dot_mask,
+                              uint32_t yout_mask, double ys1, double ys0, int run, double* out,
+                              double* yout, double* dots) {
+  ENTER(c);
+  if (ld < 0 || ld >= c->nld || ncol < 1 || ncol > MAXC || !in || !c1 || !c2 || !out ||
+      run < -1 || run > 1 || (yout_mask && !yout) || (dot_mask && !dots))
+    return fail(c, SGV_ERR_ARG, "sgv_ld_pass_ex: bad arguments");
+  const size_t M = (size_t)c->Mloc;
+  PassArgs pa{};
+  for (int j = 0; j < ncol; ++j) {
+    const bool dj = dot_mask >> j & 1u, yj = yout_mask >> j & 1u;
+    CHK(upload_vec(c, in + j * M, c->S[j]));
+    CHK(upload_vec(c, out + j * M, c->S[MAXC + j]));
+    if (yj) CHK(upload_vec(c, yout + j * M, c->S[2 * MAXC + j]));
+    if (dj && w) CHK(upload_vec(c, w + j * M, c->S[3 * MAXC + j]));
+    pa.in[j] = c->S[j];
+    pa.out[j] = c->S[MAXC + j];
+    pa.yout[j] = yj ? c->S[2 * MAXC + j] : nullptr;
+    pa.dot[j] = !dj ? nullptr : w ? c->S[3 * MAXC + j] : c->S[j];
+    pa.c1[j] = c1[j];
+    pa.c2[j] = c2[j];
+  }
+  pa.ys1 = ys1;
+  pa.ys0 = ys0;
+  if (run >= 0) {
+    if (!c->d_runw) HIPCHK(hipMalloc(&c->d_runw, sizeof(int)));
+    HIPCHK(hipMemcpy(c->d_runw, &run, sizeof(int), hipMemcpyHostToDevice));
+    pa.run = c->d_runw;
+  }
+  CHK(ld_pass(c, ld, ncol, pa));
+  if (dot_mask) {
+    CHK(reduce_dev(c, ncol, ld_parts(c, ld), identity_map(), c->d_pq));
+    HIPCHK(launch_copy_f64(c->h_tot, c->d_pq, ncol, c->st));
+  }
+  for (int j = 0; j < ncol; ++j) {
+    CHK(download_vec(c, c->S[MAXC + j], out + j * M));
+    if (yout_mask >> j & 1u) CHK(download_vec(c, c->S[2 * MAXC + j], yout + j * M));
+  }
+  if (dot_mask) std::memcpy(dots, c->h_tot, sizeof(double) * ncol);
+  resolve_timers(c);
+  return SGV_OK;
+}
+
 extern "C" int sgv_cg_solve(sgv_ctx* c, int ld, int ncol, const double* c1, const double* c2,
                             const double* b, double* x, int maxiter, double rtol, int* iters_out,
                             int* info_out) {

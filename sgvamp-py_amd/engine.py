@@ -356,6 +356,29 @@ class Engine:
         self.ctx.sgv_ld_matvec(int(ld), V.shape[0], hb.dptr(V), hb.dptr(Y))
         return Y
 
+    def ld_pass_ex(self, ld, V_local, c1, c2, w=None, dot_mask=0, yout_mask=0, ys1=0.0, ys0=0.0,
+                   run=-1, out=None, yout=None):
+        """One pass over the raw R of LD matrix ld with the whole fused epilogue
+        (sgv_ld_pass_ex): returns (out, yout, dots).  out / yout: the buffers'
+        contents before the pass (default zeros; a no-op pass returns them).
+        w None with a dot_mask: the dots alias the input columns."""
+        V = np.ascontiguousarray(np.atleast_2d(V_local), dtype=np.float64)
+        n = V.shape[0]
+        O = np.zeros_like(V) if out is None else hb.f64(out).copy()
+        Y = np.zeros_like(V) if yout is None else hb.f64(yout).copy()
+        W = None if w is None else hb.f64(w)
+        if O.shape != V.shape or Y.shape != V.shape or (W is not None and W.shape != V.shape):
+            raise ValueError("out, yout and w must have the shape of V")
+        c1, c2 = hb.f64(c1), hb.f64(c2)
+        if c1.shape != (n,) or c2.shape != (n,):
+            raise ValueError("c1 and c2 must have one entry per column")
+        dots = np.zeros(n)
+        self.ctx.sgv_ld_pass_ex(int(ld), n, hb.dptr(V), hb.dptr(c1), hb.dptr(c2),
+                                None if W is None else hb.dptr(W), int(dot_mask), int(yout_mask),
+                                float(ys1), float(ys0), int(run), hb.dptr(O), hb.dptr(Y),
+                                hb.dptr(dots))
+        return O, Y, dots
+
     def cg_solve(self, ld, c1, c2, B_local, X0_local, maxiter, rtol=1e-5):
         B = np.ascontiguousarray(np.atleast_2d(B_local), dtype=np.float64)
         X = np.ascontiguousarray(np.atleast_2d(X0_local), dtype=np.float64).copy()
