@@ -182,7 +182,7 @@ static int cg_loop_dev(sgv_ctx* c, const CgCols& cc, const double* rho0, const d
   int executed = 0;
   // one rank: iteration it's r.r reduction and the control of it + 1 are one
   // launch (k_cg_reduce_ctl), enqueued at the end of it, when that one
-  // workgroup's reduction is short (fused_ctl_pays); SGV_EM_FUSE=0 A/B
+  // workgroup's reduction is short: fused_ctl_pays alone decides (no switch)
   const bool fuse = !c->comm && !c->host_ag && fused_ctl_pays(MAXC, c->nblk);
   // exact sets pay only where fewer columns make a pass cheaper: the MFMA pass
   // (>= 3 columns of one LD matrix, cost by groups of 4); the VALU pass costs
@@ -471,7 +471,7 @@ extern "C" int sgv_em(sgv_ctx* c, const double* gam1s, const double* a, int nsla
     for (int l = 0; l < nslab; ++l) hi->om[l] = om[l];
     HIPCHK(hipMemcpyAsync(c->d_ems, hi, sizeof(EmState), hipMemcpyHostToDevice, c->st));
     for (EmArgs& e : eg) e.st = c->d_ems;
-    // one rank: reduction + control in one launch (k_em_reduce_ctl, same bits).
+    // one rank: k_em_reduce_ctl where fused_ctl_pays, else two launches (same bits).
     // With a communicator: the replicated EM (em_rep_setup) runs the same
     // one-rank loop over every rank's gathered r1.
     const bool rep = em_mode_pick(c, maxit);
