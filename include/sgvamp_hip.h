@@ -180,8 +180,11 @@ int sgv_ld_block_format(sgv_ctx* ctx, int ld, int blk_local, int* fmt_out);
  * matrix must share one precision (the first pass over a mixed matrix fails
  * with SGV_ERR_STATE, naming the matrix); different LD matrices of a context may
  * differ.  An f32 matrix runs every column count 1-16 on the 512-column MFMA
- * strips, whatever sgv_set_mfma_min says (the VALU pass, the wave-pair and wide
- * forms and the band walks are f64-only); a block's sums are a function of the
+ * strips, whatever sgv_set_mfma_min says (the VALU pass and the wave-pair and
+ * wide forms are f64-only; the band walks have float instances, but measured
+ * 1.26-1.33x the strips' time on an f32 band at 3-8 columns, so a windowed-LD
+ * matrix stored as f32 stays on the strips too and walks only with SGV_AB=1
+ * SGV_F32_WALK=1: DESIGN.md 4.4); a block's sums are a function of the
  * block alone, within 1e-12 of the f64 product of the stored values (with
  * SGV_AB=1 SGV_F32_FORM=1, the 8-byte load form, bitwise the f64 strips').
  * Measured per pass against f64: 0.53-0.57x at 2-4 columns, 0.67-0.74x at 8,

@@ -105,7 +105,8 @@ constexpr int BAND_Q = 256;
 // one (panel, column chunk) work item of k_sym_pass
 struct SymItem {
   const void* P;     // panel base: element (r0, r0); double, or float for a block stored as
-                     // f32 (one type per table: LdPlan::bits; only the strip kernels read float)
+                     // f32 (one type per table: LdPlan::bits; the strip kernels and the band
+                     // walks have float instances)
   int64_t w;         // panel row stride (elements of the stored type)
   int64_t voff;      // block's offset in the padded vector layout
   int32_t r0, H;     // panel first row (block-relative), rows
@@ -402,12 +403,13 @@ hipError_t launch_sym_mfma_wide(int nc, const SymStrip* d_strips, int nstrips,
 hipError_t launch_sym_finalize_wide(int nc, const SymPanelW* d_panels, int npanels,
                                     const PassArgs& pa, const double* rowpart,
                                     const double* colpart, double* partials, hipStream_t st);
-// band walks (NC <= 8, band_walk.hip): the walks, then the head panels' finalize
+// band walks (NC <= 8, band_walk.hip): the walks, then the head panels' finalize;
+// bits: the items' stored type (64, or 32: the float instances)
 hipError_t launch_band_walk(int nc, const SymWalk* d_walks, int nwalks, const SymPanel* d_panels,
                             const SymItem* d_items, const double* d_pk, int64_t pk_rows,
                             const PassArgs& pa, double* headbuf, double* carrybuf,
                             const WalkFin* d_fins, int nfins,
-                            double* partials, hipStream_t st);
+                            double* partials, int bits, hipStream_t st);
 hipError_t launch_sym_finalize_strip(int nc, const SymPanel* d_panels, int npanels,
                                      const PassArgs& pa, const double* rowpart,
                                      const double* colpart, double* partials, bool ragged,

@@ -391,6 +391,21 @@ static bool wide_pass(int nc) {
 // / 2.12 (profiles/r05/walk_ab/wvs_a_ab.jsonl).
 // SGV_BAND_WALK=0 (with SGV_AB=1): the strips for every band pass (the
 // walks-vs-strips A/B of tools/gpu_walk_vs_strips.sh).
+// An f32 band matrix (sgv_set_ld_precision 32) stays on the 512-column strips at
+// every column count: the walks' float instances measured 1.27-1.33x the strips'
+// time at 3-4 columns and 1.26-1.31x at 5-8 (M = 1e6, bw = 1,000 and 500, one
+// box, alternating: profiles/ld_f32_walk/ldpass_band_ab.jsonl) --
+// with half the bytes the walk is bound by its one workgroup's tile, chain and
+// hand-off work per sub-tile, which the strips spread over two workgroups per CU.
+// SGV_F32_WALK=1 (with SGV_AB=1): an f32 band-only matrix takes the walks at 3-8
+// columns, whatever sgv_set_mfma_min says (1-2 and 9-16 columns stay on the
+// strips) -- the arm of that A/B, and how the tests reach the float instances.
+// Read when the plan is built (the walk tables) and per pass (a getenv).
+constexpr int WALK_F32_MIN_NC = 3;
+static bool f32_walk_on() {
+  const char* e = ab_env("SGV_F32_WALK");
+  return e && e[0] == '1';
+}
 static int band_walk_max_nc() {
   const char* e = ab_env("SGV_BAND_WALK");
   return (e && e[0] == '0') ? 0 : 8;
@@ -411,6 +426,15 @@ static int plan_walks(sgv_ctx* c, int ld, const std::vector<SymItem>& items,
     any = true;
   }
   if (!any) return SGV_OK;
+  // float panels: the walks' 16-B form loads a float4 at columns 64 wave + 4 lane
+  // of every row of an item -- 16-B aligned only if the item's first element is
+  // and the row stride is a multiple of 4 elements
+  if (pl->bits == 32)
+    for (const SymItem& it : items)
+      if (((uintptr_t)it.P + sizeof(float) * (size_t)(it.c0 - it.r0)) % 16 != 0 || it.w % 4 != 0)
+        return fail(c, SGV_ERR_STATE,
+                    "walk plan: f32 item (r0 %d, c0 %d, row stride %lld) is not 16-byte aligned",
+                    it.r0, it.c0, (long long)it.w);
   std::vector<SymWalk> walks;
   std::vector<WalkFin> fins;
   int hs = 0, cs = 0, bp0 = 0;
@@ -591,7 +615,7 @@ int ensure_plan(sgv_ctx* c, int ld){
     }
     pl.bits = first >= 0 ? c->ldb[ld][first].bits : 64;
   }
-  const bool f32 = pl.bits == 32;   // every pass on the 512-column strips (ld_pass)
+  const bool f32 = pl.bits == 32;   // every pass on the 512-column strips (ld_pass; A/B: walks)
   std::vector<RowGroup> rg;
   std::vector<int> pbeg(c->nblk + 1, 0);
   const int rows = ld_pass_rows_per_group();
@@ -689,7 +713,7 @@ int ensure_plan(sgv_ctx* c, int ld){
     if (cls == 1) {
       CHK(build_strips(c, ld, items, panels, false, 0, &pl.s512));
       if (pl.wide.nstrips) CHK(build_strips(c, ld, items, panels, false, 2, &pl.rest));
-      if (!f32) CHK(plan_walks(c, ld, items, panels, &pl));
+      if (!f32 || f32_walk_on()) CHK(plan_walks(c, ld, items, panels, &pl));
     }
     const size_t ncmax = (size_t)sym_class_nc(cls);
     rowpart_need = std::max(rowpart_need, items.size() * SYM_H * ncmax);
@@ -754,20 +778,23 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
   if (pl.halo || pl.nctasks) CHK(coupling_pass(c, pl, nc, pa));
   if (pl.nrg) HIPCHK(launch_ld_pass(nc, c->d_blks[ld], pl.d_rg, pl.nrg, pa, c->d_part, c->st));
   if (pl.npanels) {
-    // an f32 matrix: every column count on the 512-column strips, the only
-    // kernels with float instances (its plan holds no wide strips or walks)
+    // an f32 matrix: every column count on the 512-column strips, whatever
+    // mfma_min says (its plan holds no wide strips, and walks only for the
+    // SGV_F32_WALK A/B: then a band plan's 3-8-column passes take them)
     const bool f32 = pl.bits == 32;
     const bool mf = f32 || (c->mfma_min > 0 && nc >= c->mfma_min);
     const int cls = mf ? 1 : sym_class(nc);
     if (mf) {
-      const bool walk = !f32 && pl.nwalks && nc <= band_walk_max_nc();
+      const bool walk = pl.nwalks && nc <= band_walk_max_nc() &&
+                        (!f32 || (nc >= WALK_F32_MIN_NC && f32_walk_on()));
       double mf_aux = 0.0;
       HIPCHK(launch_pk(pa, nc, c->Mpad, c->d_pk, c->st,
                        walk ? nc > 4 : strip_pk_paired(nc)));
       if (walk) {   // band plan: the walks, then the head panels
         HIPCHK(launch_band_walk(nc, pl.d_walks, pl.nwalks, pl.d_wpanels, pl.d_witems, c->d_pk,
                                 c->Mpad, pa,
-                                c->d_whead, c->d_wcarry, pl.d_wfins, pl.nwfins, c->d_part, c->st));
+                                c->d_whead, c->d_wcarry, pl.d_wfins, pl.nwfins, c->d_part, pl.bits,
+                                c->st));
       } else {
         // One strip set: group g's strips on the ctx stream, its finalize on the
         // side stream behind them, so the finalize (and the launch tail) of g

@@ -7,7 +7,8 @@ stored bytes are the band's panels (round_up(256 + bw, 256) columns per 256-row
 panel); the "csr_equiv" rate counts the 12 B per stored nonzero (8-B value +
 4-B index) a CSR mat-vec would stream instead.
 
-  python tools/ldpass_band.py --M 200000 --bw 2000 --ncols 1,2,8,16"""
+  python tools/ldpass_band.py --M 200000 --bw 2000 --ncols 1,2,8,16
+  python tools/ldpass_band.py --M 1000000 --bw 1000 --ncols 3,4,5,8 --ld-precision f32"""
 import argparse
 import hashlib
 import json
@@ -32,6 +33,8 @@ def main():
                          "(N(0, 0.02^2) off the diagonal, 1 on it; a mat-vec study, not PSD)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--ncols", default="1,2,8,16")
+    ap.add_argument("--ld-precision", default="f64", choices=["f64", "f32"],
+                    help="element type of the packed band (Engine.set_ld_precision)")
     ap.add_argument("--lib", default=None, help="A/B of builds: load this libsgvamp_hip.so")
     ap.add_argument("--tag", default="")
     a = ap.parse_args()
@@ -55,6 +58,8 @@ def main():
         A = windowed_ld(a.M, a.bw, seed=1, taps=a.taps)
     L = BlockLD.from_csr(A)
     eng = Engine(L.block_sizes, K=1)
+    if a.ld_precision == "f32":   # not called for f64: --lib may name a build without it
+        eng.set_ld_precision(32)
     for b in range(len(L.block_sizes)):
         L.upload(eng, 0, b)
     fmts = sorted({eng.ld_block_format(0, b) for b in range(len(L.block_sizes))})
@@ -69,7 +74,8 @@ def main():
             eng.ld_matvec(0, V)
         t = eng.timers()
         ms = t["ld_ms"] / t["ld_launches"]
-        print(json.dumps(dict(tag=a.tag, M=a.M, bw=a.bw, ncol=nc, ms_per_pass=ms,
+        print(json.dumps(dict(tag=a.tag, M=a.M, bw=a.bw, ncol=nc, ld_precision=a.ld_precision,
+                              ms_per_pass=ms, aux_GB=t["aux_bytes"] / t["ld_launches"] / 1e9,
                               stored_GB=t["ld_bytes"] / t["ld_launches"] / 1e9,
                               stored_GBs=t["ld_bytes"] / t["ld_launches"] / ms / 1e6,
                               frac_of_8TBs=t["ld_bytes"] / t["ld_launches"] / ms / 1e6 / 8000.0,
