@@ -271,7 +271,15 @@ int sgv_probe_draw(uint32_t* key, int32_t* pos, int64_t n, int64_t lo, int64_t h
  * SGV_STEP_CHAIN (sgv_step_begin only): gam1s, gamw (clamped to >= 1, :374),
  * alpha1_prev, alpha2_prev, *lam_io and omegas_io are taken, when the step
  * starts, from the results of the step queued before it -- so a step can be
- * queued while the previous one runs. */
+ * queued while the previous one runs.
+ * SGV_STEP_POSTERIOR (after sgv_set_posterior_outputs(ctx, 1, thr); without it
+ * the step fails with SGV_ERR_STATE): the per-marker posterior of sgv_posterior
+ * is enqueued right behind the denoiser -- the same gam1s (a chained step's: the
+ * chain's), the same r1, the prior after this step's EM / MLE update -- before
+ * the output copies.  The slot then holds (K + 4) x M_local doubles, rows K + 1
+ * .. K + 3 = pip, lodds, var, and res holds 1 + 2K + 4 + 3 doubles, the last
+ * three sgv_posterior's sums.  Everything else the step computes is bitwise what
+ * it computes without the flag. */
 #define SGV_STEP_EM 1
 #define SGV_STEP_DENOISE_DAMP 2
 #define SGV_STEP_ALPHA1_DAMP 4
@@ -280,6 +288,7 @@ int sgv_probe_draw(uint32_t* key, int32_t* pos, int64_t n, int64_t lo, int64_t h
 #define SGV_STEP_METRICS 32
 #define SGV_STEP_CHAIN 64
 #define SGV_STEP_MLE 128
+#define SGV_STEP_POSTERIOR 256
 int sgv_step(sgv_ctx* ctx, int it, int flags, int em_maxit, int nslab, const double* sigmas,
              const double* a, double* lam_io, double* omegas_io, const double* gam1s,
              double rho, const double* gamw, const double* alpha1_prev,
@@ -306,6 +315,46 @@ int sgv_step_end(sgv_ctx* ctx);
 int sgv_denoise(sgv_ctx* ctx, const double* gam1s, const double* a, double lam,
                 int nslab, const double* omegas, const double* sigmas, double rho,
                 int damp, double* der_sum_out);
+
+/* Per-marker posterior of the spike-and-slab prior at the denoiser's inputs (the
+ * context's current r1 vectors, gam1s, a and the prior lam / omegas / sigmas;
+ * no counterpart in the reference, which sums these away: pi of
+ * prior_update_em, src/sgvamp.py:131-134, and the variance inside
+ * der_denoiser_meta, :104-114).  With t = sum_k r1_k a_k gam1_k (cohort order,
+ * as the denoiser), G = sum_k a_k gam1_k, q_l = 1 / (G sigma_l + 1), s2_l =
+ * sigma_l q_l and D_l = log(lam omega_l / (1 - lam)) + (t^2 / 2) s2_l + log(q_l) / 2:
+ *   lodds = log sum_l exp(D_l), the natural log of the posterior odds of
+ *           inclusion, formed as max + log-sum-exp: finite wherever the inputs
+ *           are (|z| = 40 in 65 cohorts), where 1 - P(spike) is exactly 1;
+ *   pip   = the sigmoid of lodds, in the branch that does not cancel;
+ *   var   = Var(x | r1) by the law of total variance from non-negative terms:
+ *           with resp_l = exp(D_l - max) / sum, ms = t sum_l resp_l s2_l and vs =
+ *           sum_l resp_l s2_l + sum_l resp_l (t s2_l - ms)^2, var = pip vs +
+ *           pip (1 - pip) ms^2, 1 - pip from the sigmoid's other branch;
+ *   resp  (nullable) [nslab][M_local]: resp_l, the slab responsibilities given
+ *           inclusion (they sum to 1).
+ * lam == 0 gives pip = 0, lodds = -inf, var = 0; lam == 1 gives pip = 1, lodds =
+ * +inf, var = vs; no NaN either way.  These are the posterior at THIS r1 / gam1s
+ * / prior; xhat1 (SGV_VEC_XHAT1) is the posterior mean damped with the previous
+ * iteration's (rho), so the two differ from the second iteration on.
+ * pip_local, lodds_local, var_local: [M_local], marker order (as sgv_get_vector).
+ * sums_out[3] = sum pip (the expected number of non-null markers), sum var, and
+ * the number of markers with pip >= thr (0 <= thr <= 1), over ALL ranks' markers
+ * through the ordered reductions: bitwise independent of the block partition's
+ * spread over ranks.  Fails with SGV_ERR_STATE while a step is queued. */
+int sgv_posterior(sgv_ctx* ctx, const double* gam1s, const double* a, double lam, int nslab,
+                  const double* omegas, const double* sigmas, double thr, double* pip_local,
+                  double* lodds_local, double* var_local, double* resp_local, double* sums_out);
+/* Posterior rows in the output slots.  on != 0: the pinned slots of
+ * sgv_outputs_begin / sgv_outputs_wait are (K + 4) x M_local doubles, and steps may
+ * carry SGV_STEP_POSTERIOR (thr: the count's threshold, 0.95 customary); a step
+ * or sgv_outputs_begin without the flag then fills rows 0 .. K only.  on == 0
+ * (the default): (K + 1) x M_local, as ever.  The slots are sized when first
+ * used, so call this before the first step; a later call that changes the
+ * layout waits for the queued copies and drops the slots (buffers returned by
+ * sgv_outputs_wait become invalid), which the next sgv_outputs_begin makes again.
+ * Fails with SGV_ERR_STATE while a step is queued. */
+int sgv_set_posterior_outputs(sgv_ctx* ctx, int on, double thr);
 
 /* EM prior update loop: src/sgvamp.py:116-136 driven as :250-257 (stop when the
  * relative change of omegas and lam are both < 1e-6, at most maxit steps). */
@@ -373,7 +422,8 @@ int sgv_fsolve(int n, sgv_fsolve_fn fcn, void* user, double* x_io, double* fvec_
  * sgv_outputs_begin queues this rank's slices of xhat1 and r1[0..K-1] (unscaled,
  * marker order) into pinned slot 0, 1 or 2; sgv_outputs_wait -- callable from a
  * writer thread -- waits for that copy and returns the slot's buffer
- * [(K + 1) x M_local] doubles, valid until the slot is begun again. */
+ * [(K + 1) x M_local] doubles, valid until the slot is begun again ((K + 4) x
+ * M_local after sgv_set_posterior_outputs(ctx, 1, thr), which see). */
 int sgv_outputs_begin(sgv_ctx* ctx, int slot);
 int sgv_outputs_wait(sgv_ctx* ctx, int slot, double** data);
 

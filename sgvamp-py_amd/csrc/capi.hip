@@ -466,6 +466,8 @@ extern "C" void sgv_destroy(sgv_ctx* c) {
   if (c->d_emtot) (void)hipFree(c->d_emtot);
   if (c->d_emtab) (void)hipFree(c->d_emtab);
   if (c->d_inner) (void)hipFree(c->d_inner);
+  if (c->d_post) (void)hipFree(c->d_post);
+  if (c->h_post) (void)hipHostFree(c->h_post);
   if (c->h_emm) (void)hipHostFree(c->h_emm);
   if (c->h_emi) (void)hipHostFree(c->h_emi);
   for (hipEvent_t e : c->ev_em)
@@ -677,30 +679,67 @@ extern "C" int sgv_synth_r(sgv_ctx* c, int k, uint64_t seed, int64_t marker0, in
 // ---------------------------------------------------------------------------
 // per-iteration outputs without a host wait (src/sgvamp.py:281,283)
 // ---------------------------------------------------------------------------
-extern "C" int sgv_outputs_begin(sgv_ctx* c, int slot) {
-  ENTER(c);
+// post: the slot also takes pip, lodds, var (rows K + 1 .. K + 3) from d_post,
+// where the step's posterior kernel left them (SGV_STEP_POSTERIOR)
+int outputs_begin(sgv_ctx* c, int slot, bool post) {
   if (slot < 0 || slot >= NOUT_SLOTS) return fail(c, SGV_ERR_ARG, "slot must be 0, 1 or 2");
+  if (post && (!c->post_on || !c->d_post))
+    return fail(c, SGV_ERR_STATE, "posterior rows without sgv_set_posterior_outputs");
   const size_t n = (size_t)std::max<int64_t>(c->Mloc, 1);
-  const size_t bytes = sizeof(double) * n * (c->K + 1);
   if (!c->d_out) {   // a device staging half and a pinned buffer per slot
+    c->out_rows = c->K + 1 + (c->post_on ? POST_SUMS : 0);
+    const size_t bytes = sizeof(double) * n * c->out_rows;
     HIPCHK(hipMalloc(&c->d_out, NOUT_SLOTS * bytes));
     for (int i = 0; i < NOUT_SLOTS; ++i) {
       HIPCHK(hipHostMalloc(&c->h_out[i], bytes));
+      if (c->ev_out[i]) continue;   // kept when the buffers were resized
       HIPCHK(hipEventCreateWithFlags(&c->ev_out[i], hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&c->ev_pack[i], hipEventDisableTiming));
     }
   }
-  double* dst = c->d_out + (size_t)slot * n * (c->K + 1);
+  const int rows = c->K + 1 + (post ? POST_SUMS : 0);
+  double* dst = c->d_out + (size_t)slot * n * c->out_rows;
   HIPCHK(hipStreamWaitEvent(c->st, c->ev_out[slot], 0));   // the slot's previous copy
   HIPCHK(launch_pack(c->d_ch, c->nch, c->d_ch_doff, c->xhat1, dst, c->st));
   for (int k = 0; k < c->K; ++k)
     HIPCHK(launch_pack(c->d_ch, c->nch, c->d_ch_doff, c->r1[k], dst + n * (k + 1), c->st));
+  for (int j = 0; post && j < POST_SUMS; ++j)
+    HIPCHK(launch_pack(c->d_ch, c->nch, c->d_ch_doff, c->d_post + (size_t)j * c->Mpad,
+                       dst + n * (c->K + 1 + j), c->st));
   // the copy runs on the copy stream: the ctx stream goes on with the step
   HIPCHK(hipEventRecord(c->ev_pack[slot], c->st));
   HIPCHK(hipStreamWaitEvent(c->st_copy, c->ev_pack[slot], 0));
-  HIPCHK(hipMemcpyAsync(c->h_out[slot], dst, sizeof(double) * n * (c->K + 1),
-                        hipMemcpyDeviceToHost, c->st_copy));
+  HIPCHK(hipMemcpyAsync(c->h_out[slot], dst, sizeof(double) * n * rows, hipMemcpyDeviceToHost,
+                        c->st_copy));
   HIPCHK(hipEventRecord(c->ev_out[slot], c->st_copy));
+  return SGV_OK;
+}
+
+extern "C" int sgv_outputs_begin(sgv_ctx* c, int slot) {
+  ENTER(c);
+  return outputs_begin(c, slot, false);
+}
+
+extern "C" int sgv_set_posterior_outputs(sgv_ctx* c, int on, double thr) {
+  ENTER(c);
+  if (!(thr >= 0.0 && thr <= 1.0))
+    return fail(c, SGV_ERR_ARG, "sgv_set_posterior_outputs: thr must lie in [0, 1], got %g", thr);
+  if (c->job_ended != c->job_begun)
+    return fail(c, SGV_ERR_STATE, "sgv_set_posterior_outputs: a step is still queued");
+  c->post_on = on ? 1 : 0;
+  c->post_thr = thr;
+  if (c->d_out && c->out_rows != c->K + 1 + (c->post_on ? POST_SUMS : 0)) {
+    // slots of the other layout: dropped once their copies have landed, made
+    // again by the next sgv_outputs_begin
+    CHK(stream_wait(c));
+    HIPCHK(hipStreamSynchronize(c->st_copy));
+    HIPCHK(hipFree(c->d_out));
+    c->d_out = nullptr;
+    for (int i = 0; i < NOUT_SLOTS; ++i) {
+      HIPCHK(hipHostFree(c->h_out[i]));
+      c->h_out[i] = nullptr;
+    }
+  }
   return SGV_OK;
 }
 
@@ -708,7 +747,8 @@ extern "C" int sgv_outputs_begin(sgv_ctx* c, int slot) {
 // only waits on the slot's event and returns the pinned buffer (valid until the
 // slot's next sgv_outputs_begin).
 extern "C" int sgv_outputs_wait(sgv_ctx* c, int slot, double** data) {
-  if (!c || slot < 0 || slot >= NOUT_SLOTS || !data || !c->ev_out[slot]) return SGV_ERR_ARG;
+  if (!c || slot < 0 || slot >= NOUT_SLOTS || !data || !c->ev_out[slot] || !c->h_out[slot])
+    return SGV_ERR_ARG;
   if (hipSetDevice(c->dev) != hipSuccess) return SGV_ERR_HIP;
   hipError_t e;
   while ((e = hipEventQuery(c->ev_out[slot])) == hipErrorNotReady) __builtin_ia32_pause();

@@ -464,6 +464,28 @@ hipError_t launch_denoise(const ChunkDesc* d_ch, int nch, const DenoiseArgs& a, 
 hipError_t launch_den_inner(const ChunkDesc* d_ch, int nch, const DenoiseArgs& a, double* inner,
                             int first, hipStream_t st);
 
+// Per-marker posterior at the denoiser's inputs (posterior.hip): pip, the
+// log-odds of inclusion and Var(x | r1) per marker, optionally the slab
+// responsibilities; partials [sum pip, sum var, count(pip >= thr)] per chunk
+constexpr int POST_SUMS = 3;
+struct PosteriorArgs {
+  const double* r1[MAXK];
+  double ag[MAXK];          // a_k * gam1_k
+  int K, nslab;
+  double cw[MAXL];          // log(lam omega_l) - log1p(-lam); log(omega_l) at an edge
+  double hq[MAXL];          // log(q_l) / 2, q_l = 1 / (G sigma_l + 1)
+  double s2[MAXL];          // sigma_l q_l
+  double thr;
+  int edge;                 // -1: lam == 0 (lodds = -inf), 1: lam == 1 (+inf), 0 otherwise
+  const double* inner;      // K > MAXK: t over every cohort (launch_den_inner); then K = 1
+  double* pip;
+  double* lodds;
+  double* var;
+  double* resp[MAXL];       // null: not written
+};
+hipError_t launch_posterior(const ChunkDesc* d_ch, int nch, const PosteriorArgs& a, double* d_part,
+                            hipStream_t st);
+
 struct MleArgs {
   const double* r1[MAXK];
   double a[MAXK];

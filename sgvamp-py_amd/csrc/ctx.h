@@ -253,6 +253,16 @@ struct sgv_ctx {
   double mle_gam = std::numeric_limits<double>::quiet_NaN();
   double* d_inner = nullptr;      // K > MAXK: the denoiser's np.inner over all cohorts
   size_t inner_cap = 0;
+  // per-marker posterior outputs (sgv_posterior, SGV_STEP_POSTERIOR): pip, lodds,
+  // var and the slab responsibilities in the padded layout [3 + MAXL][Mpad], the
+  // ordered sums in pinned memory; post_on: the output slots hold K + 4 rows
+  // (sgv_set_posterior_outputs), out_rows: the rows they were allocated with
+  int post_on = 0;
+  double post_thr = 0.95;
+  double* d_post = nullptr;
+  size_t post_cap = 0;
+  double* h_post = nullptr;       // [POST_SUMS]
+  int out_rows = 0;
   size_t pk_cap = 0;
   // chunk / row-group layouts
   int nch = 0;
@@ -422,6 +432,7 @@ int probe_issue(sgv_ctx* c, int slot, int* slot_out);
 int upload_vec(sgv_ctx* c, const double* host, double* dpad);
 int download_vec(sgv_ctx* c, const double* dpad, double* host);
 bool host_any(const double* v, int64_t n);
+int outputs_begin(sgv_ctx* c, int slot, bool post);
 // exchange.hip
 int reduce_dev(sgv_ctx* c, int nv, const int* d_begin, const Map16& map, double* d_dst,
                int op = 0);

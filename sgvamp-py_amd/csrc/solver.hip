@@ -420,6 +420,91 @@ extern "C" int sgv_denoise(sgv_ctx* c, const double* gam1s, const double* a, dou
 }
 
 // ---------------------------------------------------------------------------
+// per-marker posterior at the denoiser's inputs (posterior.hip)
+// ---------------------------------------------------------------------------
+// kernel + the ordered reduction of [sum pip, sum var, count(pip >= thr)] into
+// h_post; pip, lodds, var (and with resp the nslab responsibilities) are left
+// in d_post rows 0, 1, 2 (3 + l), padded layout
+static int posterior_enqueue(sgv_ctx* c, const double* gam1s, const double* a, double lam,
+                             int nslab, const double* omegas, const double* sigmas, double thr,
+                             bool resp) {
+  if (!(lam >= 0.0 && lam <= 1.0))
+    return fail(c, SGV_ERR_ARG, "posterior: lam must lie in [0, 1], got %g", lam);
+  if (!(thr >= 0.0 && thr <= 1.0))
+    return fail(c, SGV_ERR_ARG, "posterior: thr must lie in [0, 1], got %g", thr);
+  CHK(grow(c, &c->d_post, &c->post_cap,
+           (size_t)(POST_SUMS + (resp ? nslab : 0)) * (size_t)std::max<int64_t>(c->Mpad, 1)));
+  if (!c->h_post) HIPCHK(hipHostMalloc(&c->h_post, sizeof(double) * POST_SUMS, hipHostMallocCoherent));
+  PosteriorArgs pa{};
+  DenoiseArgs da{};   // the cohort groups' np.inner (launch_den_inner)
+  double G = 0.0;
+  for (int k = 0; k < c->K; ++k) {
+    const double ag = a[k] * gam1s[k];
+    G = (k == 0) ? ag : G + ag;             // the denoiser's sum_ag
+  }
+  pa.nslab = nslab;
+  pa.thr = thr;
+  pa.edge = lam == 0.0 ? -1 : lam == 1.0 ? 1 : 0;
+  const double l1m = std::log1p(-lam);
+  for (int l = 0; l < nslab; ++l) {
+    const double q = 1.0 / (G * sigmas[l] + 1.0);
+    pa.s2[l] = sigmas[l] * q;
+    pa.hq[l] = -std::log1p(G * sigmas[l]) / 2;   // log(q_l) / 2
+    // at an edge the odds are 0 or infinite whatever the slab: the weights
+    // among the slabs (resp, var) take log(omega_l) alone
+    pa.cw[l] = pa.edge ? std::log(omegas[l]) : std::log(lam * omegas[l]) - l1m;
+    if (resp) pa.resp[l] = c->d_post + (size_t)(POST_SUMS + l) * c->Mpad;
+  }
+  pa.pip = c->d_post;
+  pa.lodds = c->d_post + c->Mpad;
+  pa.var = c->d_post + 2 * c->Mpad;
+  const int ng = (c->K + MAXK - 1) / MAXK;
+  if (ng > 1) {   // more than MAXK cohorts: t over all of them first, as the denoiser
+    CHK(grow(c, &c->d_inner, &c->inner_cap, (size_t)std::max<int64_t>(c->Mpad, 1)));
+    for (int g = 0; g < ng; ++g) {
+      da.K = std::min(MAXK, c->K - g * MAXK);
+      for (int k = 0; k < da.K; ++k) {
+        da.r1[k] = c->r1[g * MAXK + k];
+        da.ag[k] = a[g * MAXK + k] * gam1s[g * MAXK + k];
+      }
+      HIPCHK(launch_den_inner(c->d_ch, c->nch, da, c->d_inner, g == 0 ? 1 : 0, c->st));
+    }
+    pa.inner = c->d_inner;
+    pa.K = 1;
+  } else {
+    pa.K = c->K;
+    for (int k = 0; k < c->K; ++k) {
+      pa.r1[k] = c->r1[k];
+      pa.ag[k] = a[k] * gam1s[k];
+    }
+  }
+  HIPCHK(launch_posterior(c->d_ch, c->nch, pa, c->d_part, c->st));
+  CHK(reduce_dev(c, POST_SUMS, c->d_ch_begin, identity_map(), c->h_post));
+  return SGV_OK;
+}
+
+extern "C" int sgv_posterior(sgv_ctx* c, const double* gam1s, const double* a, double lam,
+                             int nslab, const double* omegas, const double* sigmas, double thr,
+                             double* pip, double* lodds, double* var, double* resp,
+                             double* sums_out) {
+  ENTER(c);
+  if (nslab < 1 || nslab > MAXL || !gam1s || !a || !omegas || !sigmas || !pip || !lodds || !var ||
+      !sums_out)
+    return fail(c, SGV_ERR_ARG, "sgv_posterior: bad arguments (nslab=%d)", nslab);
+  if (c->job_ended != c->job_begun)
+    return fail(c, SGV_ERR_STATE, "sgv_posterior: a step is still queued");
+  CHK(posterior_enqueue(c, gam1s, a, lam, nslab, omegas, sigmas, thr, resp != nullptr));
+  CHK(download_vec(c, c->d_post, pip));
+  CHK(download_vec(c, c->d_post + c->Mpad, lodds));
+  CHK(download_vec(c, c->d_post + 2 * c->Mpad, var));
+  for (int l = 0; resp && l < nslab; ++l)
+    CHK(download_vec(c, c->d_post + (size_t)(POST_SUMS + l) * c->Mpad, resp + (size_t)l * c->Mloc));
+  resolve_timers(c);
+  for (int j = 0; j < POST_SUMS; ++j) sums_out[j] = c->h_post[j];   // behind download_vec's wait
+  return SGV_OK;
+}
+
+// ---------------------------------------------------------------------------
 // EM prior loop (src/sgvamp.py:116-136, 250-257)
 // ---------------------------------------------------------------------------
 extern "C" int sgv_em(sgv_ctx* c, const double* gam1s, const double* a, int nslab,
@@ -1244,6 +1329,9 @@ static int step_impl(sgv_ctx* c, int it, int flags, int em_maxit, int nslab,
   if (!sigmas || !a || !lam_io || !omegas_io || !gam1s || !gamw || !alpha1_prev ||
       !alpha2_prev || !probes || !res || !ires || !out || !cg_out || out_slot >= NOUT_SLOTS)
     return fail(c, SGV_ERR_ARG, "sgv_step: bad arguments");
+  const bool post = (flags & SGV_STEP_POSTERIOR) != 0;
+  if (post && !c->post_on)
+    return fail(c, SGV_ERR_STATE, "SGV_STEP_POSTERIOR without sgv_set_posterior_outputs");
   const int K = c->K;
   c->chain.valid = 0;   // a step chained behind this one fails unless this one completes
   res[0] = 0.0;
@@ -1267,7 +1355,12 @@ static int step_impl(sgv_ctx* c, int it, int flags, int em_maxit, int nslab,
                       (flags & SGV_STEP_DENOISE_DAMP) ? 1 : 0, (flags & SGV_STEP_METRICS) != 0,
                       &met_fused));
   HIPCHK(hipEventRecord(c->ev_den, c->st));
-  if (out_slot >= 0) CHK(sgv_outputs_begin(c, out_slot));
+  // the posterior at the denoiser's inputs: the same gam1s and r1, the prior
+  // after this step's EM / MLE update; its rows ride in the output slot
+  if (post) {
+    CHK(posterior_enqueue(c, gam1s, a, *lam_io, nslab, omegas_io, sigmas, c->post_thr, false));
+  }
+  if (out_slot >= 0) CHK(outputs_begin(c, out_slot, post));
   if ((flags & SGV_STEP_METRICS) && !met_fused) CHK(sgv_metrics_begin(c));
   CHK(event_spin(c, c->ev_den));
   std::vector<double> der(c->h_tot, c->h_tot + K), alpha1(K), gam2(K);
@@ -1287,6 +1380,10 @@ static int step_impl(sgv_ctx* c, int it, int flags, int em_maxit, int nslab,
                 out, cg_out, &passes));
   ires[1] = passes;
   if ((flags & SGV_STEP_METRICS) && !met_fused) CHK(sgv_metrics_end(c, res + 1 + 2 * K));
+  if (post) {   // the ordered sums, queued ahead of the LMMSE: long done
+    CHK(stream_wait(c));
+    for (int j = 0; j < POST_SUMS; ++j) res[1 + 2 * K + 4 + j] = c->h_post[j];
+  }
   // inputs of a chained next step: src/sgvamp.py:347, 363-374 (gamw clamped to
   // >= 1 after it is logged, as Python's max(gamw, 1.0))
   sgv_ctx::Chain& ch = c->chain;

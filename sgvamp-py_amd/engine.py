@@ -74,6 +74,7 @@ class Engine:
             device = int(getattr(self.comm, "local_rank", 0)) if self.nranks > 1 else 0
         self.ctx = hb.Context(device, self.K, self.ld_of, self.local_sizes, self.b0,
                               len(self.block_sizes), self.M)
+        self.posterior_rows = 0     # rows behind xhat1, r1 in the output slots (set_posterior_outputs)
         self.cg_exact = cg_exact_mode(self.block_sizes)
         self.ctx.sgv_set_cg_exact(self.cg_exact)    # an SGV_CG_EXACT A/B override wins
         self.exchange = exchange or os.environ.get("SGV_EXCHANGE", "rccl")
@@ -237,18 +238,48 @@ class Engine:
                         int(maxit), hb.dptr(lam_io), hb.dptr(om), hb.iptr(steps), hb.dptr(err))
         return float(lam_io[0]), om, int(steps[0]), float(err[0])
 
+    def posterior(self, gam1s, a, lam, omegas, sigmas, thr=0.95, resp=False):
+        """The per-marker posterior at the context's current r1 (sgv_posterior):
+        dict(pip, lodds, var [Mloc], sums = [sum pip, sum var, count(pip >= thr)]
+        over all ranks, and with resp=True resp [nslab][Mloc], the slab
+        responsibilities given inclusion)."""
+        om = hb.f64(omegas)
+        sg = hb.f64(sigmas)
+        n = max(self.Mloc, 1)
+        pip, lodds, var = np.empty(n), np.empty(n), np.empty(n)
+        rsp = np.empty((len(sg), n)) if resp else None
+        if rsp is not None and n != self.Mloc:
+            raise ValueError("resp needs at least one local marker")
+        sums = np.zeros(hb.POSTERIOR_ROWS)
+        self.ctx.sgv_posterior(hb.dptr(hb.f64(gam1s)), hb.dptr(hb.f64(a)), float(lam), len(sg),
+                               hb.dptr(om), hb.dptr(sg), float(thr), hb.dptr(pip), hb.dptr(lodds),
+                               hb.dptr(var), None if rsp is None else hb.dptr(rsp), hb.dptr(sums))
+        out = dict(pip=pip[:self.Mloc], lodds=lodds[:self.Mloc], var=var[:self.Mloc], sums=sums)
+        if rsp is not None:
+            out["resp"] = rsp
+        return out
+
+    def set_posterior_outputs(self, on, thr=0.95):
+        """Posterior rows in the output slots (sgv_set_posterior_outputs): with on,
+        outputs_wait returns (K + 4, Mloc) -- rows K + 1 .. K + 3 = pip, lodds, var of
+        steps flagged hb.STEP_POSTERIOR.  Call before the first step."""
+        self.ctx.sgv_set_posterior_outputs(int(bool(on)), float(thr))
+        self.posterior_rows = hb.POSTERIOR_ROWS if on else 0
+
     def outputs_begin(self, slot):
         """Queue xhat1 and r1[k] (this rank's slice) into pinned slot 0/1 (no wait)."""
         self.ctx.sgv_outputs_begin(int(slot))
 
     def outputs_wait(self, slot):
         """Wait for slot's copy (any thread); returns a (K + 1, Mloc) view of the
-        pinned buffer, valid until the slot is begun again."""
+        pinned buffer -- (K + 4, Mloc) after set_posterior_outputs(True) -- valid
+        until the slot is begun again."""
         p = hb._c_dbl_p()
         rc = self.ctx.lib.sgv_outputs_wait(self.ctx.h, int(slot), ctypes.byref(p))
         if rc != hb.SGV_OK:
             raise hb.HipError("sgv_outputs_wait failed (%d)" % rc)
-        return np.ctypeslib.as_array(p, shape=(self.K + 1, max(self.Mloc, 1)))[:, :self.Mloc]
+        rows = self.K + 1 + self.posterior_rows
+        return np.ctypeslib.as_array(p, shape=(rows, max(self.Mloc, 1)))[:, :self.Mloc]
 
     def mle_exp_max(self, gam1s, sigma2):
         """max over (k, m, l) of (-r1_km^2 / 2) / (sigma2_l + 1/gam1_k) (src/sgvamp.py:152)."""
@@ -312,7 +343,9 @@ class Engine:
             raise ValueError("probes must be (K, Mloc) int8")
         h = dict(lam=np.array([lam], dtype=np.float64),
                  om=np.array(omegas, dtype=np.float64).copy(),
-                 pr=pr, res=np.zeros(1 + 2 * K + 4), ires=np.zeros(2, dtype=np.int32),
+                 pr=pr, ires=np.zeros(2, dtype=np.int32),
+                 res=np.zeros(1 + 2 * K + 4
+                              + (hb.POSTERIOR_ROWS if int(flags) & hb.STEP_POSTERIOR else 0)),
                  out=np.zeros((K, hb.LMMSE_NOUT)), cg=np.zeros((K, 4), dtype=np.int32))
         self.ctx.sgv_step_begin(int(it), int(flags), int(em_maxit), len(sg), hb.dptr(sg),
                                 hb.dptr(hb.f64(a)), hb.dptr(h["lam"]), hb.dptr(h["om"]),
@@ -325,14 +358,17 @@ class Engine:
 
     def step_end(self, h):
         """Wait for the oldest queued step; returns dict(lam, omegas, em_steps,
-        em_err, alpha1, gam2, metrics, out, cg, passes) (see sgv_step)."""
+        em_err, alpha1, gam2, metrics, out, cg, passes, posterior_sums) (see
+        sgv_step; posterior_sums is empty without hb.STEP_POSTERIOR)."""
         self.ctx.sgv_step_end()
         K = self.K
         return dict(lam=float(h["lam"][0]), omegas=h["om"], em_steps=int(h["ires"][0]),
                     em_err=float(h["res"][0]), mle_status=int(h["ires"][0]),
                     mle_gam=(None if np.isnan(h["res"][0]) else float(h["res"][0])),
                     alpha1=h["res"][1:1 + K].tolist(),
-                    gam2=h["res"][1 + K:1 + 2 * K].tolist(), metrics=h["res"][1 + 2 * K:],
+                    gam2=h["res"][1 + K:1 + 2 * K].tolist(),
+                    metrics=h["res"][1 + 2 * K:1 + 2 * K + 4],
+                    posterior_sums=h["res"][1 + 2 * K + 4:],
                     out=h["out"], cg=h["cg"], passes=int(h["ires"][1]))
 
     def metrics(self):

@@ -18,6 +18,8 @@ LMMSE_NOUT = 8
 O_TRSIGMA2, O_ALPHA2, O_GAM1, O_Z, O_TRRSIGMA2, O_GAMW, O_XR, O_XRX = range(8)
 STEP_EM, STEP_DENOISE_DAMP, STEP_ALPHA1_DAMP, STEP_LMMSE_DAMP, STEP_LEARN_GAMW, STEP_METRICS, \
     STEP_CHAIN, STEP_MLE = 1, 2, 4, 8, 16, 32, 64, 128
+STEP_POSTERIOR = 256     # pip, lodds, var rows in the output slot, three sums behind res
+POSTERIOR_ROWS = 3
 MLE_NOT_CONVERGED, MLE_NEGATIVE = 1, 2
 OUT_SLOTS = 3
 MAX_COHORTS = 1024
@@ -72,6 +74,9 @@ _SIGS = {
     "sgv_synth_r": [_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, _c_dbl_p],
     "sgv_denoise": [_vp, _c_dbl_p, _c_dbl_p, ctypes.c_double, ctypes.c_int, _c_dbl_p, _c_dbl_p,
                     ctypes.c_double, ctypes.c_int, _c_dbl_p],
+    "sgv_posterior": [_vp, _c_dbl_p, _c_dbl_p, ctypes.c_double, ctypes.c_int, _c_dbl_p, _c_dbl_p,
+                      ctypes.c_double, _c_dbl_p, _c_dbl_p, _c_dbl_p, _c_dbl_p, _c_dbl_p],
+    "sgv_set_posterior_outputs": [_vp, ctypes.c_int, ctypes.c_double],
     "sgv_em": [_vp, _c_dbl_p, _c_dbl_p, ctypes.c_int, _c_dbl_p, ctypes.c_int, _c_dbl_p, _c_dbl_p,
                _c_int_p, _c_dbl_p],
     "sgv_lmmse": [_vp, ctypes.c_int, _c_dbl_p, _c_dbl_p, _c_dbl_p, _c_dbl_p, _c_i8_p, ctypes.c_int,

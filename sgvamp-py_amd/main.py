@@ -13,6 +13,9 @@ Same flags, defaults, validation messages, log lines and output files
   copies of it;
 * --seed (extension): seeds the Hutchinson probes per cohort, RandomState(seed+k)
   (the reference draws from the unseeded global RNG, src/sgvamp.py:326);
+* --posterior last|all, --pip-threshold (extensions): per-marker posterior
+  files {name}_pip_it_{it}.bin, {name}_lodds_it_{it}.bin, {name}_postvar_it_{it}.bin
+  and {name}_posterior.csv (sgvamp.VAMP's docstring); off by default;
 * --bim-files may be omitted when every cohort has the same marker order;
 * LD may also be given as a block manifest (*.blocks.json, see ldio.py).
 """
@@ -32,6 +35,7 @@ from comm import world_from_env  # noqa: E402
 from ldio import load_ld, load_plink_ld_all, load_r, load_true_signal, merge_bims  # noqa: E402
 from sgvamp import BlockLD  # noqa: E402
 from sgvamp import VAMP  # noqa: E402
+from sgvamp import check_pip_threshold  # noqa: E402
 
 
 def build_parser():
@@ -67,7 +71,19 @@ def build_parser():
                         "world size, else 1)", default=None)
     parser.add_argument("--ld-precision", choices=["f64", "f32"], default="f64",
                         help="Element type packed LD blocks are stored in: f32 rounds R once, at load, to the nearest f32, half the LD memory; all arithmetic stays f64 (the exact f64 solve of R perturbed by <= 2^-24 relative per entry)")
+    parser.add_argument("--posterior", choices=["none", "last", "all"], default="none",
+                        help="Per-marker posterior files of the last or of all iterations: <name>_pip_it_<it>.bin (posterior inclusion probability), <name>_lodds_it_<it>.bin (log posterior odds of inclusion, finite in the tails where 1 - pip underflows), <name>_postvar_it_<it>.bin (posterior variance on the xhat file's scale squared), and <name>_posterior.csv (it, sum_pip, sum_postvar, n_pip_ge_thr); they are the posterior at that iteration's r1, gam1 and prior, whereas xhat is the damped mean (rho); none writes no new file")
+    parser.add_argument("--pip-threshold", type=pip_threshold_arg, default=0.95,
+                        help="Threshold of the posterior.csv count n_pip_ge_thr (markers with pip >= it), a probability in [0, 1]; used with --posterior last or all")
     return parser
+
+
+def pip_threshold_arg(text):
+    """argparse type of --pip-threshold: a float in [0, 1]."""
+    try:
+        return check_pip_threshold(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not a probability in [0, 1]" % (text,))
 
 
 def main(argv=None):
@@ -206,7 +222,9 @@ def main(argv=None):
                prior_vars=prior_vars_list, prior_probs=prior_probs_list, out_dir=out_dir,
                out_name=out_name, comm=comm, seed=seed,
                device=None if args.device is None else int(args.device),
-               ld_precision=args.ld_precision)
+               ld_precision=args.ld_precision,
+               posterior=None if args.posterior == "none" else args.posterior,
+               pip_threshold=args.pip_threshold)
     if rank == 0:
         logging.info("...Running sgVAMP\n")
     ts = time.time()

@@ -303,12 +303,38 @@ def common_partition(size_lists):
 
 
 LD_PRECISIONS = {"f64": 64, "f32": 32}   # ld_precision -> Engine.set_ld_precision bits
+POSTERIOR_MODES = (None, "last", "all")  # iterations whose per-marker posterior is written
+
+
+def check_pip_threshold(thr):
+    """The PIP count's threshold as a float in [0, 1]; ValueError otherwise."""
+    try:
+        t = float(thr)
+    except (TypeError, ValueError):
+        t = float("nan")
+    if not 0.0 <= t <= 1.0:
+        raise ValueError("pip_threshold must be a probability in [0, 1], not %r" % (thr,))
+    return t
 
 
 class VAMP:
+    """``posterior`` ("last" or "all"; None: off) adds, per selected iteration, the
+    per-marker posterior of the spike-and-slab prior to the output files:
+    ``<name>_pip_it_<it>.bin`` (the posterior inclusion probability),
+    ``<name>_lodds_it_<it>.bin`` (the natural log of the posterior odds of
+    inclusion, finite where 1 - pip underflows) and ``<name>_postvar_it_<it>.bin``
+    (Var(x | r1) / Nt, the square of the xhat file's scale; pip and lodds are
+    unscaled), and ``<name>_posterior.csv`` with it, sum_pip, sum_postvar and
+    n_pip_ge_thr (the markers with pip >= ``pip_threshold``).  The xhat file holds
+    the damped posterior mean (rho times this iteration's plus 1 - rho times the
+    previous file's); the pip, lodds and postvar files are the posterior at this
+    iteration's r1, gam1 and prior alone, so from the second iteration on they
+    describe a slightly different distribution than the one xhat averages."""
+
     def __init__(self, N, Nt, M, K, rho, gamw, gam1, a, prior_vars, prior_probs, out_dir,
                  out_name, comm=None, seed=None, device=None, write_files=True, ld_packing=True,
-                 exchange=None, mfma_min=None, rs_recurrence=None, ld_precision="f64"):
+                 exchange=None, mfma_min=None, rs_recurrence=None, ld_precision="f64",
+                 posterior=None, pip_threshold=0.95):
         # src/sgvamp.py:15-31
         self.eps = 1e-32
         self.K = int(K)
@@ -349,7 +375,11 @@ class VAMP:
             raise ValueError("ld_precision='f32' needs ld_packing=True: only packed LD blocks "
                              "are stored as f32")
         self.ld_precision = ld_precision
-        self.mfma_min = mfma_min       # None: library default (f64 MFMA pass from 3 RHS)
+        if posterior not in POSTERIOR_MODES:
+            raise ValueError("posterior must be None, 'last' or 'all', not %r" % (posterior,))
+        self.posterior_mode = posterior
+        self.pip_threshold = check_pip_threshold(pip_threshold)
+        self.mfma_min = mfma_min      # None: library default (f64 MFMA pass from 3 RHS)
         self.rs_recurrence = rs_recurrence   # None: library default (R_s x carried, no gamw pass)
         self.gam = None
         self.engine = None
@@ -369,6 +399,16 @@ class VAMP:
                     ["it", "gamw", "gam1", "gam2", "alpha1", "alpha2", "lam"])
         with open(os.path.join(self.out_dir, "%s_metrics.csv" % self.out_name), "w", newline="") as f:
             csv.writer(f, delimiter="\t").writerow(["it", "alignment", "l2"])
+        if self.posterior_mode is not None:
+            with open(os.path.join(self.out_dir, "%s_posterior.csv" % self.out_name), "w",
+                      newline="") as f:
+                csv.writer(f, delimiter="\t").writerow(
+                    ["it", "sum_pip", "sum_postvar", "n_pip_ge_thr"])
+
+    def write_posterior_to_file(self, row):
+        with open(os.path.join(self.out_dir, "%s_posterior.csv" % self.out_name), "a",
+                  newline="") as f:
+            csv.writer(f, delimiter="\t").writerow(row)
 
     def write_params_to_file(self, params, cohort_idx):
         with open(os.path.join(self.out_dir, "%s_cohort_%d.csv" % (self.out_name, cohort_idx + 1)),
@@ -401,6 +441,26 @@ class VAMP:
 
     def write_r1_to_file(self, it, r1_local, k):
         self._write_slice("%s_r1_cohort_%d_it_%d.bin" % (self.out_name, k, it), r1_local)
+
+    def write_posterior_vector_to_file(self, it, kind, local):
+        """kind: "pip", "lodds" (both unscaled) or "postvar" (Var(x | r1) / Nt)."""
+        self._write_slice("%s_%s_it_%d.bin" % (self.out_name, kind, it), local)
+
+    def _post_it(self, it):
+        """Whether iteration it's per-marker posterior is computed and written."""
+        if self.posterior_mode == "all":
+            return True
+        return self.posterior_mode == "last" and it == self._n_iter - 1
+
+    def posterior(self):
+        """The per-marker posterior at the current state (call after finish()):
+        dict(pip, lodds, var: this rank's marker slice, sums = [sum pip, sum var,
+        markers with pip >= pip_threshold] over all ranks), in the library's scale
+        (the postvar file is var / Nt).  It is the posterior at the r1 vectors,
+        gam1 and prior the last iteration left, NOT the distribution xhat is the
+        mean of: xhat is the damped mean (rho)."""
+        return self.engine.posterior(np.array(self._st["gam1"], dtype=np.float64), self.a,
+                                     self.lam, self.omegas, self.sigmas, self.pip_threshold)
 
     # ---- set-up ----------------------------------------------------------------
     def _setup(self, R, r, x0):
@@ -443,6 +503,8 @@ class VAMP:
                                           exchange=self.exchange)
         eng.set_ld_packing(self.ld_packing)
         eng.set_ld_precision(LD_PRECISIONS[self.ld_precision])
+        if self.posterior_mode is not None:   # before the first step: the slots' layout
+            eng.set_posterior_outputs(True, self.pip_threshold)
         if self.mfma_min is not None:
             eng.set_mfma_min(self.mfma_min)
         if self.rs_recurrence is not None:
@@ -479,6 +541,8 @@ class VAMP:
         self.engine = engine
         self._begun = False
         engine.update_cg_exact()   # collective: every rank attaches its engine
+        if self.posterior_mode is not None:
+            engine.set_posterior_outputs(True, self.pip_threshold)
         for k in range(self.K):
             engine.set_vector(hb.VEC_R1, k, engine.get_vector(hb.VEC_R, k))
             engine.set_cohort_n(k, self.N_list[k])
@@ -506,8 +570,11 @@ class VAMP:
         engine was attached).  `iterations`: the number of step() calls that will
         follow (0, 1, ...); when known, step(it) queues step it + 1 behind it."""
         self._n_iter = iterations
+        if self.posterior_mode == "last" and iterations is None:
+            raise ValueError("posterior='last' needs the iteration count: infer(), or "
+                             "begin(iterations=...)")
         self._queued = None
-        self._xhat_loc = {}        # iteration -> local xhat1 (return_xhat with files)
+        self._xhat_loc = {}       # iteration -> local xhat1 (return_xhat with files)
         self._writes = []          # (iteration, future) of the output-file writers
         self._unwritten = []       # finished iterations whose files are not started
         if self.engine is None:
@@ -605,8 +672,27 @@ class VAMP:
         for k in range(self.K):
             futs.append(self._write_pool.submit(
                 lambda k=k: self.write_r1_to_file(it, out[k + 1] / np.sqrt(Nt), k + 1)))   # :283
+        # (the phases path writes them from Engine.posterior: _step_phases)
+        if self._post_it(it) and hb.ab_env("SGV_STEP") != "phases":
+            futs += self._posterior_writers(it, out[self.K + 1], out[self.K + 2], out[self.K + 3])
         for f in futs:
             f.result()
+
+    def _posterior_writers(self, it, pip, lodds, var):
+        """One task per posterior file of iteration it: pip and lodds as they are,
+        postvar = var / Nt (the square of the xhat file's 1 / sqrt(Nt))."""
+        Nt = self.Nt
+        w = self.write_posterior_vector_to_file
+        return [self._write_pool.submit(lambda: w(it, "pip", pip)),
+                self._write_pool.submit(lambda: w(it, "lodds", lodds)),
+                self._write_pool.submit(lambda: w(it, "postvar", var / Nt))]
+
+    def _posterior_row(self, it, sums, rec):
+        """The iteration's posterior.csv row from the ordered sums (rank 0 writes)."""
+        row = [it, float(sums[0]), float(sums[1]) / self.Nt, int(sums[2])]
+        rec["posterior_sums"] = tuple(row[1:])
+        if self.rank == 0 and self.write_files:
+            self._queue_csv(self.write_posterior_to_file, row)
 
     def flush(self):
         """Wait for the output files of every finished iteration."""
@@ -688,6 +774,8 @@ class VAMP:
             flags |= hb.STEP_LEARN_GAMW
         if self._has_x0:
             flags |= hb.STEP_METRICS                                  # :379-387
+        if self._post_it(it):
+            flags |= hb.STEP_POSTERIOR
         return flags
 
     def _take_probes(self, rec):
@@ -866,6 +954,8 @@ class VAMP:
                 logging.debug("L2_error(xhat1, x0) = %0.9f \n", l2)
                 if self.write_files:
                     self._queue_csv(self.write_metrics_to_file, [it, alignment, l2])
+        if flags & hb.STEP_POSTERIOR:
+            self._posterior_row(it, r["posterior_sums"], rec)
         rec.update(gamw=list(gamw), gam1=list(gam1), gam2=gam2, alpha1=list(alpha1),
                    alpha2=list(alpha2), lam=self.lam, wall_s=time.perf_counter() - t_it)
         self.history.append(rec)
@@ -921,8 +1011,16 @@ class VAMP:
             rec["wait_write_ms"] = (time.perf_counter() - t0) * 1e3
             eng.outputs_begin(it % 2)
             self._pending_write = self._out_pool.submit(self._write_outputs, it, it % 2)
+        if self._post_it(it):
+            # the same inputs as the denoiser just had: gam1s, r1, the updated prior
+            p = eng.posterior(gam1s, self.a, self.lam, self.omegas, self.sigmas,
+                              self.pip_threshold)
+            if self.write_files:
+                for f in self._posterior_writers(it, p["pip"], p["lodds"], p["var"]):
+                    self._writes.append((it, f))
+            self._posterior_row(it, p["sums"], rec)
         if self._has_x0:
-            eng.metrics_begin()       # of xhat1, read back at the end (:379-387)
+            eng.metrics_begin()      # of xhat1, read back at the end (:379-387)
         if st["return_xhat"]:
             xhat_loc = eng.get_vector(hb.VEC_XHAT1)
             full = xhat_loc
