@@ -241,6 +241,46 @@ int sgv_synth_ld_g(sgv_ctx* ctx, int ld, uint64_t geno_seed, int64_t marker0, in
 int sgv_synth_r(sgv_ctx* ctx, int k, uint64_t geno_seed, int64_t marker0, int Nsamp,
                 const double* y);
 
+/* ---- genotype LD source: PLINK 1 .bed rows -> LD blocks, r and g ----------
+ * The reference's simulation/sim_phen.py:33-37,58-59 (bed_reader's default: x =
+ * count of A1; X standardised per marker; r = X^T y / sqrt(N)) and the LD R =
+ * X^T X / N of the same genotypes, formed on the device from the 2-bit codes
+ * without X, G or R ever existing on the host.
+ * A row is one marker, SNP-major: sample n has code (row[n / 4] >> 2 (n % 4)) & 3,
+ * 0 = homozygous A1 (x = 2), 1 = missing, 2 = heterozygous (x = 1), 3 =
+ * homozygous A2 (x = 0); the bits past sample nsamp of the last byte are padding
+ * and are never counted.  Per marker, over its observed samples, in exact
+ * integers: n_obs, S1 = sum x, S2 = sum x^2; mean = S1 / n_obs, sd = sqrt((n_obs
+ * S2 - S1^2) / n_obs^2); G[i][n] = ((x - mean) / sd) / sqrt(nsamp), 0 where
+ * missing (mean imputation), so R_ii = n_obs_i / nsamp.  A marker with n_obs = 0
+ * or n_obs S2 = S1^2 (one value among its observed samples) has no LD.
+ *
+ * sgv_geno_set_block: rows = the block's n_b rows (block-local marker order),
+ * consecutive rows row_bytes apart (>= ceil(nsamp / 4); no alignment needed).
+ * Copies them to the device, keeps them and the per-marker tables there until
+ * the next call for the block, sgv_geno_clear or sgv_destroy, and returns
+ * counts_out[i * 4 + code] = samples of marker i with that code (n_b x 4).  Bad
+ * shapes are SGV_ERR_ARG.  Markers without LD are not an error here: the caller
+ * finds them in the counts (and reports them before asking for LD).
+ * sgv_geno_ld: R_b = G_b G_b^T of block blk_local into LD matrix ld, in the
+ * context's packing (sgv_set_ld_packing) and precision (sgv_set_ld_precision: 32
+ * rounds each f64 sum once, on store), as sgv_synth_ld_g stores its blocks; the
+ * device memory it needs beyond the block is the rows (n_b ceil(nsamp / 16) 4
+ * bytes) whatever nsamp.  SGV_ERR_STATE, with the stored block (if any) left as
+ * it was, when the block has no genotypes or a marker without LD.
+ * sgv_geno_r: r_k = G y over every owned block (y: nsamp doubles).
+ * sgv_geno_g: g_blocks_out[b * nsamp + n] = sum_{i in b} X_std[i][n] beta_i, X_std
+ * = sqrt(nsamp) G, beta_i == 0 skipped (nblk x nsamp, as sgv_synth_ld_g).
+ * Both need genotypes of one nsamp, without such markers, in every owned block
+ * (SGV_ERR_STATE otherwise).
+ * sgv_geno_clear frees the rows and tables of every block. */
+int sgv_geno_set_block(sgv_ctx* ctx, int blk_local, const uint8_t* rows, int64_t row_bytes,
+                       int nsamp, int64_t* counts_out);
+int sgv_geno_ld(sgv_ctx* ctx, int ld, int blk_local);
+int sgv_geno_r(sgv_ctx* ctx, int k, const double* y);
+int sgv_geno_g(sgv_ctx* ctx, const double* beta_local, double* g_blocks_out);
+int sgv_geno_clear(sgv_ctx* ctx);
+
 /* ---- Hutchinson probes (host only, no device) ----------------------------
  * src/sgvamp.py:326 u = np.random.binomial(p=1/2, n=1, size=n)*2-1 from a legacy
  * numpy RandomState (MT19937) whose state is key[624], *pos (as

@@ -413,6 +413,11 @@ extern "C" void sgv_destroy(sgv_ctx* c) {
   for (auto& v : c->ldb)
     for (LdBlock& lb : v) free_block(lb);
   for (LdPlan& pl : c->plan) free_plan(pl);
+  for (GenoBlock& gb : c->geno) {
+    if (gb.d_bits) (void)hipFree(gb.d_bits);
+    if (gb.d_lut) (void)hipFree(gb.d_lut);
+    if (gb.d_msd) (void)hipFree(gb.d_msd);
+  }
   for (auto& v : c->cpl)
     for (LdCoupling& q : v) {
       if (q.d_up) (void)hipFree(q.d_up);
@@ -673,6 +678,149 @@ extern "C" int sgv_synth_r(sgv_ctx* c, int k, uint64_t seed, int64_t marker0, in
     HIPCHK(launch_row_dot(sb.G, n, Nsamp, ldg, sb.g, c->r[k] + c->bvoff[b], c->st));
   }
   CHK(stream_wait(c));
+  return SGV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// genotype LD source: PLINK .bed rows -> LD blocks, r and g (geno.hip)
+// ---------------------------------------------------------------------------
+static void geno_free(GenoBlock& gb) {
+  if (gb.d_bits) (void)hipFree(gb.d_bits);
+  if (gb.d_lut) (void)hipFree(gb.d_lut);
+  if (gb.d_msd) (void)hipFree(gb.d_msd);
+  gb = GenoBlock();
+}
+
+extern "C" int sgv_geno_clear(sgv_ctx* c) {
+  ENTER(c);
+  CHK(stream_wait(c));
+  for (GenoBlock& gb : c->geno) geno_free(gb);
+  c->geno.clear();
+  return SGV_OK;
+}
+
+extern "C" int sgv_geno_set_block(sgv_ctx* c, int b, const uint8_t* rows, int64_t row_bytes,
+                                  int nsamp, int64_t* counts_out) {
+  ENTER(c);
+  if (b < 0 || b >= c->nblk || !rows || !counts_out || nsamp < 1 ||
+      row_bytes < ((int64_t)nsamp + 3) / 4)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_set_block: bad arguments (block %d, %d samples, rows of "
+                "%lld bytes)", b, nsamp, (long long)row_bytes);
+  const int64_t n = c->bn[b];
+  const int64_t used = ((int64_t)nsamp + 3) / 4;
+  const int64_t stride_w = ((int64_t)nsamp + 15) / 16;
+  const size_t bits_bytes = (size_t)n * stride_w * 4;
+  const size_t cnt_bytes = sizeof(long long) * 4 * (size_t)n;
+  if (c->geno.empty()) c->geno.resize(c->nblk);
+  GenoBlock& gb = c->geno[b];
+  geno_free(gb);
+  HIPCHK(hipMalloc(&gb.d_bits, bits_bytes));
+  HIPCHK(hipMalloc(&gb.d_lut, sizeof(double) * 4 * n));
+  HIPCHK(hipMalloc(&gb.d_msd, sizeof(double) * 2 * n));
+  gb.stride_w = stride_w;
+  gb.nsamp = nsamp;
+  // rows need not be word aligned in the file: repacked to whole words (zero
+  // filled: padding the kernels mask) in the pinned staging buffer
+  CHK(ensure_hstage(c, std::max(bits_bytes, cnt_bytes)));
+  CHK(ensure_stage(c, cnt_bytes));
+  uint8_t* hs = static_cast<uint8_t*>(c->h_stage);
+  std::memset(hs, 0, bits_bytes);
+  for (int64_t i = 0; i < n; ++i)
+    std::memcpy(hs + (size_t)i * stride_w * 4, rows + (size_t)i * row_bytes, (size_t)used);
+  HIPCHK(hipMemcpyAsync(gb.d_bits, hs, bits_bytes, hipMemcpyHostToDevice, c->st));
+  long long* d_cnt = static_cast<long long*>(c->d_stage);
+  HIPCHK(launch_bed_stats(gb.d_bits, stride_w, (int)n, nsamp, d_cnt, gb.d_lut, gb.d_msd, c->st));
+  CHK(stream_wait(c));   // the bits have left the staging buffer
+  HIPCHK(hipMemcpyAsync(c->h_stage, d_cnt, cnt_bytes, hipMemcpyDeviceToHost, c->st));
+  CHK(stream_wait(c));
+  const long long* hc = static_cast<const long long*>(c->h_stage);
+  gb.nbad = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const long long c0 = hc[4 * i], c2 = hc[4 * i + 2], c3 = hc[4 * i + 3];
+    const long long nobs = c0 + c2 + c3, S1 = 2 * c0 + c2, S2 = 4 * c0 + c2;
+    if (nobs == 0 || nobs * S2 - S1 * S1 == 0) ++gb.nbad;
+    for (int k = 0; k < 4; ++k) counts_out[4 * i + k] = (int64_t)hc[4 * i + k];
+  }
+  return SGV_OK;
+}
+
+// every owned block holds usable genotypes of nsamp samples (nsamp < 0: any, returned)
+static int geno_ready(sgv_ctx* c, const char* who, int* nsamp_io) {
+  if ((int)c->geno.size() != c->nblk)
+    return fail(c, SGV_ERR_STATE, "%s: no genotypes set (sgv_geno_set_block)", who);
+  for (int b = 0; b < c->nblk; ++b) {
+    const GenoBlock& gb = c->geno[b];
+    if (!gb.d_bits) return fail(c, SGV_ERR_STATE, "%s: block %d has no genotypes", who, b);
+    if (gb.nbad)
+      return fail(c, SGV_ERR_STATE, "%s: block %d has %lld marker(s) without LD (monomorphic or "
+                  "unobserved)", who, b, (long long)gb.nbad);
+    if (*nsamp_io < 0) *nsamp_io = gb.nsamp;
+    if (gb.nsamp != *nsamp_io)
+      return fail(c, SGV_ERR_STATE, "%s: block %d holds %d samples, not %d", who, b, gb.nsamp,
+                  *nsamp_io);
+  }
+  return SGV_OK;
+}
+
+extern "C" int sgv_geno_ld(sgv_ctx* c, int ld, int b) {
+  ENTER(c);
+  if (ld < 0 || ld >= c->nld || b < 0 || b >= c->nblk)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_ld: bad arguments (ld %d, block %d)", ld, b);
+  if ((int)c->geno.size() != c->nblk || !c->geno[b].d_bits)
+    return fail(c, SGV_ERR_STATE, "sgv_geno_ld: block %d has no genotypes (sgv_geno_set_block)", b);
+  const GenoBlock& gb = c->geno[b];
+  if (gb.nbad)   // before any storage changes: the block stays as it was
+    return fail(c, SGV_ERR_STATE, "sgv_geno_ld: block %d has %lld marker(s) without LD "
+                "(monomorphic or unobserved)", b, (long long)gb.nbad);
+  CHK(ld_alloc(c, ld, b, c->packing));    // R = G G^T is exactly symmetric
+  const LdBlock& lb = c->ldb[ld][b];
+  HIPCHK(launch_bed_syrk(gb.d_bits, gb.stride_w, gb.d_lut, (int)c->bn[b], gb.nsamp, lb.ptr,
+                         c->lda[b], lb.fmt, lb.d_poff, lb.d_pw, lb.bits, c->st));
+  CHK(stream_wait(c));
+  std::fill(c->rx0_valid.begin(), c->rx0_valid.end(), 0);
+  return SGV_OK;
+}
+
+extern "C" int sgv_geno_r(sgv_ctx* c, int k, const double* y) {
+  ENTER(c);
+  if (k < 0 || k >= c->K || !y) return fail(c, SGV_ERR_ARG, "sgv_geno_r: bad arguments");
+  int nsamp = -1;
+  CHK(geno_ready(c, "sgv_geno_r", &nsamp));
+  if (c->nblk == 0) return SGV_OK;
+  SynthBufs sb;
+  HIPCHK(hipMalloc(&sb.g, sizeof(double) * nsamp));
+  CHK(h2d(c, y, sizeof(double) * nsamp));
+  HIPCHK(hipMemcpyAsync(sb.g, c->d_stage, sizeof(double) * nsamp, hipMemcpyDeviceToDevice, c->st));
+  for (int b = 0; b < c->nblk; ++b) {
+    const GenoBlock& gb = c->geno[b];
+    HIPCHK(launch_bed_row_dot(gb.d_bits, gb.stride_w, gb.d_lut, (int)c->bn[b], nsamp, sb.g,
+                              c->r[k] + c->bvoff[b], c->st));
+  }
+  CHK(stream_wait(c));
+  return SGV_OK;
+}
+
+extern "C" int sgv_geno_g(sgv_ctx* c, const double* beta, double* g_out) {
+  ENTER(c);
+  if (!beta || !g_out) return fail(c, SGV_ERR_ARG, "sgv_geno_g: bad arguments");
+  int nsamp = -1;
+  CHK(geno_ready(c, "sgv_geno_g", &nsamp));
+  if (c->nblk == 0) return SGV_OK;
+  SynthBufs sb;
+  HIPCHK(hipMalloc(&sb.vec, sizeof(double) * std::max<int64_t>(c->Mloc, 1)));
+  HIPCHK(hipMalloc(&sb.g, sizeof(double) * nsamp));
+  CHK(h2d(c, beta, sizeof(double) * c->Mloc));
+  HIPCHK(hipMemcpyAsync(sb.vec, c->d_stage, sizeof(double) * c->Mloc, hipMemcpyDeviceToDevice,
+                        c->st));
+  CHK(ensure_hstage(c, sizeof(double) * nsamp));
+  for (int b = 0; b < c->nblk; ++b) {
+    const GenoBlock& gb = c->geno[b];
+    HIPCHK(launch_bed_g_accum(gb.d_bits, gb.stride_w, gb.d_msd, (int)c->bn[b], nsamp,
+                              sb.vec + c->boff[b], sb.g, c->st));
+    HIPCHK(hipMemcpyAsync(c->h_stage, sb.g, sizeof(double) * nsamp, hipMemcpyDeviceToHost, c->st));
+    CHK(stream_wait(c));
+    std::memcpy(g_out + (size_t)b * nsamp, c->h_stage, sizeof(double) * nsamp);
+  }
   return SGV_OK;
 }
 

@@ -710,4 +710,20 @@ hipError_t launch_g_accum(uint64_t seed, int64_t gmarker0, int n, int nsamp, con
 hipError_t launch_row_dot(const double* d_G, int n, int nsamp, int ldg, const double* d_y,
                           double* d_out, hipStream_t st);
 
+
+// Genotype LD source (geno.hip): PLINK .bed rows at a stride of stride_w 32-bit
+// words on the device ---------------------------------------------------------
+// counts[i][4] (codes 0..3 over the nsamp samples), lut[i][4] = t_i[code],
+// msd[i] = {mean, sd}
+hipError_t launch_bed_stats(const uint32_t* d_bits, int64_t stride_w, int n, int nsamp,
+                            long long* d_counts, double* d_lut, double* d_msd, hipStream_t st);
+// R = G G^T from the bits (launch_syrk_nt's layouts and rounding; G is not formed)
+hipError_t launch_bed_syrk(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int n,
+                           int nsamp, void* d_R, int64_t lda, int packed, const int64_t* d_poff,
+                           const int64_t* d_pw, int bits, hipStream_t st);
+hipError_t launch_bed_row_dot(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int n,
+                              int nsamp, const double* d_y, double* d_out, hipStream_t st);
+hipError_t launch_bed_g_accum(const uint32_t* d_bits, int64_t stride_w, const double* d_msd, int n,
+                              int nsamp, const double* d_beta, double* d_g, hipStream_t st);
+
 }  // namespace sgv

@@ -59,6 +59,17 @@ struct LdCoupling {
   double* d_lo = nullptr;   // C (nr x nc): side 1, on gb + 1's rank
 };
 
+// genotypes of one owned block (sgv_geno_set_block): the .bed rows at a stride of
+// whole 32-bit words, the per-marker tables of k_bed_stats
+struct GenoBlock {
+  uint32_t* d_bits = nullptr;    // [n][stride_w]
+  double* d_lut = nullptr;       // [n][4] t_i[code]
+  double* d_msd = nullptr;       // [n][2] mean, sd
+  int64_t stride_w = 0;
+  int nsamp = 0;
+  int64_t nbad = 0;              // markers without LD (monomorphic or unobserved)
+};
+
 // launch tables of one LD matrix (rebuilt when a block's storage changes)
 // Strip tables of one MFMA strip kernel family over some of a plan's packed
 // blocks (build_strips): strips in dispatch order, their items in strip order,
@@ -185,6 +196,7 @@ struct sgv_ctx {
   std::vector<BlkDesc*> d_blks;
   std::vector<LdPlan> plan;
   std::vector<std::vector<LdCoupling>> cpl;   // [ld]: couplings of band pieces
+  std::vector<GenoBlock> geno;   // [b]: genotype LD source (empty until sgv_geno_set_block)
   std::vector<int> rank_blk0;    // first global block of each rank, then nblk_global
   double* d_cpbuf = nullptr;     // coupling sums [slot][256][nc]
   size_t cpbuf_cap = 0;

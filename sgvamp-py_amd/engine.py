@@ -219,6 +219,49 @@ class Engine:
         y = np.ascontiguousarray(y, dtype=np.float64)
         self.ctx.sgv_synth_r(int(k), int(geno_seed), self.marker0, int(nsamp), hb.dptr(y))
 
+    # ---- genotype LD source (PLINK .bed rows, device) -------------------------
+    def geno_set_block(self, b_global, rows, nsamp):
+        """Stage the .bed rows of block b_global (uint8, one row per marker, at
+        least ceil(nsamp / 4) bytes each) if this rank owns it; returns the
+        (n_b, 4) int64 counts of the codes 0..3 per marker, or None."""
+        if not (self.b0 <= b_global < self.b1):
+            return None
+        rows = np.asarray(rows)
+        n = self.block_sizes[b_global]
+        if rows.dtype != np.uint8 or rows.ndim != 2 or rows.shape[0] != n \
+                or rows.shape[1] < (int(nsamp) + 3) // 4 or int(nsamp) < 1:
+            raise ValueError("genotype rows of block %d: %s %s, expected uint8 (%d, >= %d)"
+                             % (b_global, rows.dtype, rows.shape, n, (int(nsamp) + 3) // 4))
+        rows = np.ascontiguousarray(rows)
+        counts = np.empty((n, 4), dtype=np.int64)
+        self.ctx.sgv_geno_set_block(b_global - self.b0, rows.ctypes.data_as(hb._c_u8_p),
+                                    int(rows.shape[1]), int(nsamp),
+                                    counts.ctypes.data_as(hb._c_i64_p))
+        return counts
+
+    def geno_ld(self, ld, b_global):
+        """R_b = G_b G_b^T of the staged genotypes into LD matrix ld (this rank's
+        block; the engine's packing and precision)."""
+        if not (self.b0 <= b_global < self.b1):
+            return
+        self.ctx.sgv_geno_ld(int(ld), b_global - self.b0)
+
+    def geno_r(self, k, y):
+        """r_k = G y over this rank's blocks (get_vector(VEC_R, k) reads it)."""
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        self.ctx.sgv_geno_r(int(k), hb.dptr(y))
+
+    def geno_g(self, beta_full, nsamp):
+        """Per owned block g_b = X_std,b^T beta_b: (local blocks, nsamp)."""
+        beta = np.ascontiguousarray(np.asarray(beta_full, dtype=np.float64).ravel()[self.sl])
+        g = np.empty((len(self.local_sizes), int(nsamp)), dtype=np.float64)
+        self.ctx.sgv_geno_g(hb.dptr(beta), hb.dptr(g))
+        return g
+
+    def geno_clear(self):
+        """Free the staged genotypes and their tables."""
+        self.ctx.sgv_geno_clear()
+
     # ---- hot path ------------------------------------------------------------
     def denoise(self, gam1s, a, lam, omegas, sigmas, rho, damp):
         out = np.zeros(self.K)

@@ -31,6 +31,7 @@ _c_int_p = ctypes.POINTER(ctypes.c_int)
 _c_i64_p = ctypes.POINTER(ctypes.c_int64)
 _c_dbl_p = ctypes.POINTER(ctypes.c_double)
 _c_i8_p = ctypes.POINTER(ctypes.c_int8)
+_c_u8_p = ctypes.POINTER(ctypes.c_uint8)
 _vp = ctypes.c_void_p
 
 # name -> argtypes (restype int unless listed in _RESTYPES)
@@ -72,6 +73,11 @@ _SIGS = {
     "sgv_synth_ld_g": [_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, _c_dbl_p,
                        _c_dbl_p],
     "sgv_synth_r": [_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, _c_dbl_p],
+    "sgv_geno_set_block": [_vp, ctypes.c_int, _c_u8_p, ctypes.c_int64, ctypes.c_int, _c_i64_p],
+    "sgv_geno_ld": [_vp, ctypes.c_int, ctypes.c_int],
+    "sgv_geno_r": [_vp, ctypes.c_int, _c_dbl_p],
+    "sgv_geno_g": [_vp, _c_dbl_p, _c_dbl_p],
+    "sgv_geno_clear": [_vp],
     "sgv_denoise": [_vp, _c_dbl_p, _c_dbl_p, ctypes.c_double, ctypes.c_int, _c_dbl_p, _c_dbl_p,
                     ctypes.c_double, ctypes.c_int, _c_dbl_p],
     "sgv_posterior": [_vp, _c_dbl_p, _c_dbl_p, ctypes.c_double, ctypes.c_int, _c_dbl_p, _c_dbl_p,

@@ -12,6 +12,10 @@
               cohort (the reference's MPI point-to-point exchange, emulated here in one
               process: load_plink_ld_all)
 * true signal: .bin (f64) / .npy, multiplied by sqrt(N) (main.py:268-285)
+* genotypes:  a PLINK 1 .bed/.bim/.fam panel (read_bed) as an LD source: BedLD
+              forms each LD block on the device from the block's 2-bit rows
+              (simulation/sim_phen.py:33-37 reads such a panel with bed_reader;
+              here NumPy only)
 """
 import json
 import os
@@ -175,3 +179,223 @@ def load_true_signal(path, M, N):
     if path.endswith(".npy"):
         return np.load(path) * np.sqrt(N)
     raise Exception("Unsupported true signal format!")
+
+
+# ---------------------------------------------------------------------------
+# PLINK 1 .bed panels as an LD source
+# ---------------------------------------------------------------------------
+BED_MAGIC = b"\x6c\x1b"
+BED_A1_COUNT = np.array([2.0, np.nan, 1.0, 0.0])   # value of a 2-bit code (1 = missing)
+
+
+def _bed_prefix(path):
+    return path[:-4] if path.endswith(".bed") else path
+
+
+class BedPanel:
+    """A PLINK 1 .bed/.bim/.fam panel: ``rows`` is a read-only memmap (M,
+    ceil(N / 4)) of the SNP-major 2-bit codes, ``N`` the .fam sample count,
+    ``ids`` the .bim variant ids (row order)."""
+
+    def __init__(self, prefix, rows, N, ids):
+        self.prefix, self.rows, self.N, self.ids = prefix, rows, int(N), list(ids)
+        self._index = None
+
+    @property
+    def M(self):
+        return len(self.ids)
+
+    def index_of(self, variants):
+        """Panel rows of the given variant ids, in their order; a variant the
+        panel lacks is an error that gives the count."""
+        if self._index is None:
+            self._index = {v: i for i, v in enumerate(self.ids)}
+        ix = self._index
+        missing = [v for v in variants if v not in ix]
+        if missing:
+            raise ValueError("%d of %d variant(s) are absent from the panel %s.bim (first: %s)"
+                             % (len(missing), len(variants), self.prefix,
+                                ", ".join(str(v) for v in missing[:5])))
+        return np.array([ix[v] for v in variants], dtype=np.int64)
+
+
+def read_bed(prefix):
+    """Open the panel prefix.bed / .bim / .fam (a path ending in .bed is accepted).
+    Only the SNP-major layout is read: magic 6c 1b 01, then per variant ceil(N / 4)
+    bytes, sample n in bits 2 (n % 4) of byte n // 4."""
+    prefix = _bed_prefix(prefix)
+    with open(prefix + ".fam") as f:
+        N = sum(1 for line in f if line.strip())
+    with open(prefix + ".bim") as f:
+        ids = [line.split()[1] for line in f if line.strip()]
+    bed = prefix + ".bed"
+    with open(bed, "rb") as f:
+        head = f.read(3)
+    if len(head) < 3 or head[:2] != BED_MAGIC:
+        raise ValueError("%s is not a PLINK 1 .bed file (magic bytes %s, expected 6c 1b)"
+                         % (bed, head[:2].hex(" ")))
+    if head[2] != 1:
+        raise ValueError("%s is in sample-major mode (third byte %02x): only SNP-major .bed "
+                         "files (01) are read; convert it with plink --make-bed" % (bed, head[2]))
+    if N < 1:
+        raise ValueError("%s.fam lists no sample" % prefix)
+    M, nb = len(ids), (N + 3) // 4
+    size = os.path.getsize(bed)
+    if size != 3 + M * nb:
+        raise ValueError("%s has %d bytes, expected 3 + %d variants x %d bytes = %d for the %d "
+                         "samples of its .fam" % (bed, size, M, nb, 3 + M * nb, N))
+    rows = np.memmap(bed, dtype=np.uint8, mode="r", offset=3, shape=(M, nb)) if M else \
+        np.zeros((0, nb), dtype=np.uint8)
+    return BedPanel(prefix, rows, N, ids)
+
+
+def write_bed(prefix, codes, bim_rows, fam_rows):
+    """Write prefix.bed / .bim / .fam.  codes: (M, N) 2-bit PLINK codes (0 hom A1,
+    1 missing, 2 het, 3 hom A2); bim_rows / fam_rows: one sequence of the six
+    columns (or one ready line) per variant / sample."""
+    prefix = _bed_prefix(prefix)
+    codes = np.asarray(codes)
+    if codes.ndim != 2 or len(bim_rows) != codes.shape[0] or len(fam_rows) != codes.shape[1]:
+        raise ValueError("codes must be (len(bim_rows), len(fam_rows))")
+    if codes.size and (codes.min() < 0 or codes.max() > 3):
+        raise ValueError("codes must be in 0..3")
+    M, N = codes.shape
+    nb = (N + 3) // 4
+    pad = np.zeros((M, nb * 4), dtype=np.uint8)
+    pad[:, :N] = codes
+    q = pad.reshape(M, nb, 4)
+    rows = q[:, :, 0] | (q[:, :, 1] << 2) | (q[:, :, 2] << 4) | (q[:, :, 3] << 6)
+    with open(prefix + ".bed", "wb") as f:
+        f.write(BED_MAGIC + b"\x01")
+        f.write(np.ascontiguousarray(rows, dtype=np.uint8).tobytes())
+    for ext, table in ((".bim", bim_rows), (".fam", fam_rows)):
+        with open(prefix + ext, "w") as f:
+            for row in table:
+                f.write((row if isinstance(row, str) else "\t".join(str(x) for x in row)) + "\n")
+    return prefix
+
+
+def bed_codes(rows, N):
+    """(n, N) uint8 codes of packed .bed rows (the padding bits dropped)."""
+    rows = np.asarray(rows, dtype=np.uint8)
+    sh = np.array([0, 2, 4, 6], dtype=np.uint8)
+    return ((rows[:, :, None] >> sh) & 3).reshape(rows.shape[0], -1)[:, :N]
+
+
+def equal_blocks(M, n):
+    """M markers in blocks of n, the last one shorter."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("LD block size must be >= 1")
+    return [n] * (M // n) + ([M % n] if M % n else [])
+
+
+class BedLD(BlockLD):
+    """Block-diagonal LD whose blocks are marker ranges of a genotype panel:
+    R_b = G_b G_b^T with G the per-marker standardised A1 counts / sqrt(N),
+    missing genotypes mean-imputed (include/sgvamp_hip.h, "genotype LD source").
+
+    upload() sends only the block's 2-bit rows; the device forms R_b in the
+    engine's packing and precision, so a rank reads only its own part of the
+    .bed and no matrix exists on the host or on disk.  block() is the same
+    definition evaluated on the host in NumPy (n x N doubles and an f64
+    product: slow, for checks and for regroup(), which on the same partition
+    returns this object and on a coarser one a plain BlockLD whose blocks are
+    assembled on the host from block() -- the slow path).  ``select``: panel rows in marker
+    order (default: the panel's own order)."""
+
+    uses_geno = True
+
+    def __init__(self, panel, block_sizes, select=None, s=0.0):
+        sizes = [int(b) for b in block_sizes]
+        super().__init__(block_sizes=sizes, loader=self._host_block, s=s)
+        self.panel = panel
+        self.select = None if select is None else np.asarray(select, dtype=np.int64)
+        m = panel.M if self.select is None else len(self.select)
+        if sum(sizes) != m or any(b < 1 for b in sizes):
+            raise ValueError("LD block sizes sum to %d, the panel selection has %d markers"
+                             % (sum(sizes), m))
+        self._offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+    def _index(self, b):
+        o0, o1 = int(self._offs[b]), int(self._offs[b + 1])
+        return np.arange(o0, o1) if self.select is None else self.select[o0:o1]
+
+    def rows(self, b):
+        """The block's packed rows, (n_b, ceil(N / 4)) uint8."""
+        ix = self._index(b)
+        if len(ix) and np.all(np.diff(ix) == 1):   # one contiguous read of the file
+            return np.ascontiguousarray(self.panel.rows[int(ix[0]):int(ix[-1]) + 1])
+        return np.ascontiguousarray(self.panel.rows[ix])
+
+    def variant_ids(self, b):
+        return [self.panel.ids[i] for i in self._index(b)]
+
+    def check_counts(self, b, counts):
+        """ValueError naming the block's markers that have no LD (no observed
+        sample, or one value among them), from their code counts."""
+        c = np.asarray(counts, dtype=np.int64)
+        nobs = c[:, 0] + c[:, 2] + c[:, 3]
+        s1 = 2 * c[:, 0] + c[:, 2]
+        s2 = 4 * c[:, 0] + c[:, 2]
+        bad = np.flatnonzero((nobs == 0) | (nobs * s2 - s1 * s1 == 0))
+        if len(bad):
+            ids = self.variant_ids(b)
+            raise ValueError("%d marker(s) of LD block %d have no LD (monomorphic among their "
+                             "observed samples, or all missing): %s%s"
+                             % (len(bad), b, ", ".join(str(ids[i]) for i in bad[:5]),
+                                ", ..." if len(bad) > 5 else ""))
+
+    def standardised(self, b):
+        """G_b (n_b, N) on the host, and the code counts."""
+        N = self.panel.N
+        codes = bed_codes(self.rows(b), N)
+        counts = np.stack([(codes == k).sum(axis=1) for k in range(4)], axis=1).astype(np.int64)
+        self.check_counts(b, counts)
+        nobs = counts[:, 0] + counts[:, 2] + counts[:, 3]
+        s1 = 2 * counts[:, 0] + counts[:, 2]
+        s2 = 4 * counts[:, 0] + counts[:, 2]
+        mean = s1.astype(np.float64) / nobs.astype(np.float64)
+        sd = np.sqrt((nobs * s2 - s1 * s1).astype(np.float64)
+                     / (nobs.astype(np.float64) * nobs.astype(np.float64)))
+        x = BED_A1_COUNT[codes]
+        G = ((x - mean[:, None]) / sd[:, None]) / np.sqrt(float(N))
+        G[codes == 1] = 0.0
+        return G, counts
+
+    def _host_block(self, b):
+        G, _ = self.standardised(b)
+        return G @ G.T
+
+    def block_csr(self, b):
+        return None
+
+    def band_width(self, b):
+        return None
+
+    def upload(self, eng, ld, b, packed=True):
+        """Stage block b's rows on the engine and form R_b there (this rank's
+        blocks only; `packed` is the engine's own setting)."""
+        if not (eng.b0 <= b < eng.b1):
+            return
+        counts = eng.geno_set_block(b, self.rows(b), self.panel.N)
+        self.check_counts(b, counts)
+        eng.geno_ld(ld, b)
+
+
+def load_bed_ld(path, s, block_size=None, blocks_file=None, variants=None):
+    """A .bed panel as a BedLD: blocks of block_size markers (the last shorter) or
+    the sizes listed one per line in blocks_file; variants: the marker order as
+    variant ids (default: the panel's own)."""
+    panel = read_bed(path)
+    select = None if variants is None else panel.index_of(list(variants))
+    M = panel.M if select is None else len(select)
+    if blocks_file is not None:
+        with open(blocks_file) as f:
+            sizes = [int(t) for t in f.read().split()]
+        if sum(sizes) != M:
+            raise ValueError("%s lists blocks of %d markers in all, the LD has %d"
+                             % (blocks_file, sum(sizes), M))
+    else:
+        sizes = equal_blocks(M, block_size)
+    return BedLD(panel, sizes, select=select, s=s)

@@ -17,7 +17,14 @@ Same flags, defaults, validation messages, log lines and output files
   files {name}_pip_it_{it}.bin, {name}_lodds_it_{it}.bin, {name}_postvar_it_{it}.bin
   and {name}_posterior.csv (sgvamp.VAMP's docstring); off by default;
 * --bim-files may be omitted when every cohort has the same marker order;
-* LD may also be given as a block manifest (*.blocks.json, see ldio.py).
+* LD may also be given as a block manifest (*.blocks.json, see ldio.py);
+* LD may be a genotype panel: an --ld-files entry ending in .bed (PLINK 1
+  .bed/.bim/.fam) is turned into LD blocks on the device, each rank reading only
+  its own blocks' rows.  The blocks come from --ld-block-size n (equal blocks,
+  the last shorter) or --ld-blocks FILE (one size per line); exactly one of the
+  two is required.  With --bim-files the panel's rows are matched to the merged
+  marker order by variant id (ids only, no allele reconciliation, as the
+  reference matches); without, the panel's own order is used.
 """
 import argparse
 import logging
@@ -32,7 +39,8 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 from comm import world_from_env  # noqa: E402
-from ldio import load_ld, load_plink_ld_all, load_r, load_true_signal, merge_bims  # noqa: E402
+from ldio import load_bed_ld, load_ld, load_plink_ld_all, load_r, load_true_signal  # noqa: E402
+from ldio import merge_bims  # noqa: E402
 from sgvamp import BlockLD  # noqa: E402
 from sgvamp import VAMP  # noqa: E402
 from sgvamp import check_pip_threshold  # noqa: E402
@@ -75,7 +83,31 @@ def build_parser():
                         help="Per-marker posterior files of the last or of all iterations: <name>_pip_it_<it>.bin (posterior inclusion probability), <name>_lodds_it_<it>.bin (log posterior odds of inclusion, finite in the tails where 1 - pip underflows), <name>_postvar_it_<it>.bin (posterior variance on the xhat file's scale squared), and <name>_posterior.csv (it, sum_pip, sum_postvar, n_pip_ge_thr); they are the posterior at that iteration's r1, gam1 and prior, whereas xhat is the damped mean (rho); none writes no new file")
     parser.add_argument("--pip-threshold", type=pip_threshold_arg, default=0.95,
                         help="Threshold of the posterior.csv count n_pip_ge_thr (markers with pip >= it), a probability in [0, 1]; used with --posterior last or all")
+    parser.add_argument("--ld-block-size", default=None,
+                        help="With a .bed LD source: LD blocks of this many markers (the last one shorter)")
+    parser.add_argument("--ld-blocks", default=None,
+                        help="With a .bed LD source: file listing the LD block sizes, one per line")
     return parser
+
+
+def check_bed_flags(parser, args):
+    """A .bed LD source needs exactly one of --ld-block-size / --ld-blocks; the
+    flags mean nothing without one."""
+    bed = any(p.endswith(".bed") for p in (args.ld_files or "").split(","))
+    given = (args.ld_block_size is not None) + (args.ld_blocks is not None)
+    if bed and given == 0:
+        parser.error("a .bed LD source needs its LD blocks: give --ld-block-size n or --ld-blocks FILE")
+    if given == 2:
+        parser.error("--ld-block-size and --ld-blocks exclude each other: give exactly one")
+    if given and not bed:
+        parser.error("--ld-block-size / --ld-blocks apply to a .bed LD source only")
+    if args.ld_block_size is not None:
+        try:
+            ok = int(args.ld_block_size) >= 1
+        except ValueError:
+            ok = False
+        if not ok:
+            parser.error("--ld-block-size must be a positive integer, not %r" % (args.ld_block_size,))
 
 
 def pip_threshold_arg(text):
@@ -87,7 +119,9 @@ def pip_threshold_arg(text):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_bed_flags(parser, args)
     if argv is None:            # command line: --gpus N starts the ranks (before any GPU call)
         from launch import relaunch
 
@@ -199,7 +233,12 @@ def main(argv=None):
         for k in range(K):
             p = ld_fpaths_list[k]
             if p not in by_path:
-                by_path[p] = load_ld(p, s)
+                if p.endswith(".bed"):   # genotypes: the blocks are formed on the device
+                    by_path[p] = load_bed_ld(
+                        p, s, block_size=args.ld_block_size, blocks_file=args.ld_blocks,
+                        variants=bim_ref if bim_fpaths is not None else None)
+                else:
+                    by_path[p] = load_ld(p, s)
             lds.append(by_path[p])
     for L in lds:
         if L.M != M:

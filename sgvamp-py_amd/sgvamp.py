@@ -516,6 +516,8 @@ class VAMP:
             for gb in sorted(couplings[l]):   # every rank, every coupling (collective)
                 nr, nc, C = couplings[l][gb]
                 eng.set_ld_coupling(l, gb, nr, nc, C)
+        if any(getattr(L, "uses_geno", False) for L in uniq):
+            eng.geno_clear()   # the blocks are stored: the staged genotype rows can go
         eng.update_cg_exact()   # the run's CG column sets from the bytes stored (collective)
         rr = np.asarray(r, dtype=np.float64)
         rr = rr.reshape(K, -1) if rr.size == K * self.M else rr

@@ -20,6 +20,16 @@ Outputs (prefix --out):
   {out}_{k}.bim               variants rs0.. at coordinates 1..M (main.py's --bim-files)
 
     python simulate.py --out sim/c --N 10000 --M 1000000 --K 4 --block-size 15625 --shared-ld 1
+
+--bed PREFIX instead simulates a phenotype on a real PLINK 1 panel
+(simulation/sim_phen.py:28-63 restated): X = the panel's A1 counts standardised
+per marker (missing genotypes at the mean), beta with int(M lam) causal markers
+~ N(0, h2 / CV), y = X beta + N(0, 1 - h2), r = X^T y / sqrt(N), the
+standardisation, X beta and X^T y on the device straight from the 2-bit rows.
+N and M are the panel's.  Outputs, the reference's names and shapes:
+  {out}_phen.npy (N, 1)   {out}_bet.npy (M, 1)   {out}_r.npy (M, 1)
+
+    python simulate.py --bed panel --out sim/p --h2 0.8 --lam 0.5 --seed 1
 """
 import argparse
 import json
@@ -123,8 +133,49 @@ def simulate(out, N, M, K=2, h2=0.8, lam=0.5, block_size=None, shared_ld=False, 
     return paths
 
 
+BED_SIM_BLOCK = 16384   # markers staged per block by simulate_bed (any value: the same sums)
+
+
+def simulate_bed(bed, out, h2=0.8, lam=0.5, seed=2025, block_size=None, device=None):
+    """Phenotype on the panel `bed` (prefix or .bed path); returns the paths."""
+    from ldio import BedLD, equal_blocks, read_bed
+
+    panel = read_bed(bed)
+    N, M = panel.N, panel.M
+    cv = int(M * lam)                                   # sim_phen.py:41
+    if cv < 1:
+        raise ValueError("int(M * lam) = %d causal markers: nothing to simulate" % cv)
+    rs = np.random.RandomState(seed)
+    beta = np.zeros(M)
+    beta[rs.choice(M, cv, replace=False)] = rs.normal(0, np.sqrt(h2 / cv), cv)   # :44-47
+    L = BedLD(panel, equal_blocks(M, block_size or min(M, BED_SIM_BLOCK)))
+    eng = Engine(L.block_sizes, K=1, device=device)
+    try:
+        for b in range(eng.b0, eng.b1):
+            L.check_counts(b, eng.geno_set_block(b, L.rows(b), N))
+        g = eng.geno_g(beta, N).sum(axis=0)             # :48, block by block in order
+        w = rs.normal(0.0, np.sqrt(1 - h2), N)          # :50-52
+        y = g + w
+        eng.geno_r(0, y)                                # :58-59
+        r = eng.get_vector(hb.VEC_R, 0)
+    finally:
+        eng.close()
+    print("Causal variants = %d" % cv)
+    print("Var(g) =", np.var(g))
+    print("Var(y) =", np.var(y))
+    print("h2 =", np.var(g) / np.var(y))
+    paths = {"phen": out + "_phen.npy", "beta": out + "_bet.npy", "r": out + "_r.npy"}
+    np.save(paths["phen"], y.reshape(N, 1))
+    np.save(paths["beta"], beta.reshape(M, 1))
+    np.save(paths["r"], r.reshape(M, 1))
+    return paths
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
+    p.add_argument("-bed", "--bed", help="PLINK 1 panel (prefix or .bed path): simulate a "
+                   "phenotype on its genotypes instead of drawing synthetic cohorts",
+                   default=None)
     p.add_argument("-out", "--out", help="Output path")
     p.add_argument("-N", "--N", help="Number of samples")
     p.add_argument("-M", "--M", help="Number of markers")
@@ -139,6 +190,14 @@ def main(argv=None):
                    help="Element type the on-device generator stores R in: f32 rounds G G^T "
                         "(computed in f64) once, on store, and halves the LD memory")
     a = p.parse_args(argv)
+    if a.bed is not None:
+        print("...Phenotype simulation for sgVAMP\n")
+        paths = simulate_bed(a.bed, a.out, h2=float(a.h2), lam=float(a.lam), seed=int(a.seed),
+                             block_size=int(a.block_size) if a.block_size else None,
+                             device=int(a.device) if a.device is not None else None)
+        print("main.py inputs: --ld-files %s.bed --r-files %s --true-signal-file %s"
+              % (a.bed[:-4] if a.bed.endswith(".bed") else a.bed, paths["r"], paths["beta"]))
+        return
     print("...Simulating data for sgVAMP\n")
     paths = simulate(a.out, int(a.N), int(a.M), K=int(a.K), h2=float(a.h2), lam=float(a.lam),
                      block_size=int(a.block_size) if a.block_size else None,
