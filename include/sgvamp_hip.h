@@ -38,7 +38,9 @@ extern "C" {
 
 /* ABI revision of this header.  2: sgv_timers / sgv_exchange_stats take the
  * caller's buffer length (cap), sgv_comm_info added.  An integrator checks
- * sgv_abi_version() == SGV_ABI_VERSION before binding the rest. */
+ * sgv_abi_version() == SGV_ABI_VERSION before binding the rest.  Entry points
+ * added since (sgv_posterior, the sgv_geno_* family) change no existing
+ * signature or layout and leave the revision at 2. */
 #define SGV_ABI_VERSION 2
 int sgv_abi_version(void);
 
@@ -280,6 +282,40 @@ int sgv_geno_ld(sgv_ctx* ctx, int ld, int blk_local);
 int sgv_geno_r(sgv_ctx* ctx, int k, const double* y);
 int sgv_geno_g(sgv_ctx* ctx, const double* beta_local, double* g_blocks_out);
 int sgv_geno_clear(sgv_ctx* ctx);
+
+/* ---- windowed genotype LD: packed bands and their couplings from the bits ---
+ * With a window W >= 1, counted in markers of the run's marker order (block-
+ * local row order here), inside each LD block:
+ *   R_b[i][j] = (G_b G_b^T)[i][j]  if |i - j| <= W,
+ *   R_b[i][j] = exactly 0.0        otherwise,
+ * G as above (same counts, mean, sd, mean imputation, R_ii = n_obs_i / nsamp).
+ * Every stored entry is the same sample-sequential sum sgv_geno_ld forms, so the
+ * band equals the masked dense-triangle block entry for entry and does not
+ * depend on where a band is cut into pieces.  Truncating LD to a window does not
+ * preserve positive semi-definiteness (as PLINK's --ld-window); the ridge
+ * (sgv_set_ridge) is the remedy.
+ *
+ * sgv_geno_ld_band: block blk_local of LD matrix ld from the rows staged by
+ * sgv_geno_set_block, stored by sgv_set_ld_block_csr's rule: with bw = min(window,
+ * n - 1) a packed band of panel extent round_up(256 + bw, 256) columns, or the
+ * packed triangle (still masked to the window) where that extent is >= n; in the
+ * context's precision (sgv_set_ld_precision).  The block is indistinguishable
+ * from the same matrix uploaded as CSR.  SGV_ERR_ARG: window < 1; SGV_ERR_STATE:
+ * packing is off (a band is a packed layout), or -- the stored block (if any)
+ * left as it was -- the block has no genotypes or a marker without LD.
+ * sgv_geno_coupling: the coupling between band pieces gb and gb + 1 (see
+ * sgv_set_ld_coupling) from genotypes: rows = the last nr rows of piece gb, then
+ * the first nc rows of piece gb + 1 (nr + nc rows, row_bytes apart).  Forms C =
+ * G_tail G_head^T on the device, entry (a, c) kept iff c + nr - a <= window (the
+ * two markers' distance), with precision 32 each entry rounded once to f32, and
+ * registers it as sgv_set_ld_coupling does, so cut pieces plus couplings are
+ * exactly the uncut band.  The same collective contract: every rank calls it for
+ * every coupling; rows and counts_out may be NULL where the rank owns neither
+ * piece.  counts_out[i * 4 + code] as sgv_geno_set_block's ((nr + nc) x 4);
+ * SGV_ERR_STATE, nothing registered, when a row has no LD. */
+int sgv_geno_ld_band(sgv_ctx* ctx, int ld, int blk_local, int64_t window);
+int sgv_geno_coupling(sgv_ctx* ctx, int ld, int gb, int nr, int nc, const uint8_t* rows,
+                      int64_t row_bytes, int nsamp, int64_t window, int64_t* counts_out);
 
 /* ---- Hutchinson probes (host only, no device) ----------------------------
  * src/sgvamp.py:326 u = np.random.binomial(p=1/2, n=1, size=n)*2-1 from a legacy

@@ -781,6 +781,117 @@ extern "C" int sgv_geno_ld(sgv_ctx* c, int ld, int b) {
   return SGV_OK;
 }
 
+// windowed R_b: a packed band (or, where the band is as wide as the triangle, the
+// packed triangle) by sgv_set_ld_block_csr's allocation rule, zeroed, then the
+// in-window entries from the bits
+extern "C" int sgv_geno_ld_band(sgv_ctx* c, int ld, int b, int64_t window) {
+  ENTER(c);
+  if (ld < 0 || ld >= c->nld || b < 0 || b >= c->nblk)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band: bad arguments (ld %d, block %d)", ld, b);
+  if (window < 1)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band: window %lld (must be >= 1 marker)",
+                (long long)window);
+  if (!c->packing)
+    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band: a band is a packed layout and packing is off "
+                "(sgv_set_ld_packing)");
+  if ((int)c->geno.size() != c->nblk || !c->geno[b].d_bits)
+    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band: block %d has no genotypes "
+                "(sgv_geno_set_block)", b);
+  const GenoBlock& gb = c->geno[b];
+  if (gb.nbad)   // before any storage changes: the block stays as it was
+    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band: block %d has %lld marker(s) without LD "
+                "(monomorphic or unobserved)", b, (long long)gb.nbad);
+  const int64_t n = c->bn[b];
+  if (n > (int64_t)65535 * 64)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band: block %d has %lld markers, at most %lld are "
+                "formed in one piece", b, (long long)n, (long long)65535 * 64);
+  const int64_t bw = std::min<int64_t>(window, n - 1);
+  int64_t ext = round_up(SYM_H + bw, BAND_Q);
+  if (ext >= n) ext = 0;   // the band is as wide as the triangle
+  CHK(ld_alloc(c, ld, b, 1, ext));
+  const LdBlock& lb = c->ldb[ld][b];
+  // a block kept from an earlier call of the same shape may hold a wider window
+  const int64_t g1 = (int64_t)lb.poff.size() - 1;
+  const size_t elems = (size_t)(lb.poff[g1] + (n - g1 * SYM_H) * lb.pw[g1]);
+  HIPCHK(hipMemsetAsync(lb.ptr, 0, lb.esz() * elems, c->st));
+  HIPCHK(launch_bed_syrk_band(gb.d_bits, gb.stride_w, gb.d_lut, (int)n, gb.nsamp, bw, ext, lb.ptr,
+                              lb.d_poff, lb.d_pw, lb.bits, c->st));
+  CHK(stream_wait(c));
+  std::fill(c->rx0_valid.begin(), c->rx0_valid.end(), 0);
+  return SGV_OK;
+}
+
+// coupling gb from the halo's rows: staged, counted and tabulated as a block's,
+// C formed on the device, downloaded and registered as sgv_set_ld_coupling's
+extern "C" int sgv_geno_coupling(sgv_ctx* c, int ld, int gb, int nr, int nc, const uint8_t* rows,
+                                 int64_t row_bytes, int nsamp, int64_t window,
+                                 int64_t* counts_out) {
+  ENTER(c);
+  if (ld < 0 || ld >= c->nld || gb < 0 || gb + 1 >= c->nblk_global || nr < 1 || nc < 1)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling: bad arguments (ld %d, gb %d, %d x %d)", ld, gb,
+                nr, nc);
+  if (window < 1)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling: window %lld (must be >= 1 marker)",
+                (long long)window);
+  const int ba = gb - c->blk0, bb = gb + 1 - c->blk0;
+  const bool own = (ba >= 0 && ba < c->nblk) || (bb >= 0 && bb < c->nblk);
+  if (!own) return ld_set_coupling(c, "sgv_geno_coupling", ld, gb, nr, nc, nullptr);
+  if (!rows || !counts_out || nsamp < 1 || row_bytes < ((int64_t)nsamp + 3) / 4)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling: bad rows (coupling %d, %d samples, rows of "
+                "%lld bytes)", gb, nsamp, (long long)row_bytes);
+  if ((ba >= 0 && ba < c->nblk && nr > c->bn[ba]) || (bb >= 0 && bb < c->nblk && nc > c->bn[bb]))
+    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling: %d x %d exceeds the pieces", nr, nc);
+  const int64_t n = (int64_t)nr + nc;
+  const int64_t used = ((int64_t)nsamp + 3) / 4;
+  const int64_t stride_w = ((int64_t)nsamp + 15) / 16;
+  const size_t bits_bytes = (size_t)n * stride_w * 4;
+  const size_t cnt_bytes = sizeof(long long) * 4 * (size_t)n;
+  const size_t c_bytes = sizeof(double) * (size_t)nr * nc;
+  GenoBlock h;       // the halo's rows and tables, freed on every way out
+  struct Guard {
+    GenoBlock& g;
+    double* d_C = nullptr;
+    ~Guard() {
+      geno_free(g);
+      if (d_C) (void)hipFree(d_C);
+    }
+  } guard{h};
+  HIPCHK(hipMalloc(&h.d_bits, bits_bytes));
+  HIPCHK(hipMalloc(&h.d_lut, sizeof(double) * 4 * n));
+  HIPCHK(hipMalloc(&h.d_msd, sizeof(double) * 2 * n));
+  HIPCHK(hipMalloc(&guard.d_C, c_bytes));
+  CHK(ensure_hstage(c, std::max(std::max(bits_bytes, cnt_bytes), c_bytes)));
+  CHK(ensure_stage(c, cnt_bytes));
+  uint8_t* hs = static_cast<uint8_t*>(c->h_stage);
+  std::memset(hs, 0, bits_bytes);
+  for (int64_t i = 0; i < n; ++i)
+    std::memcpy(hs + (size_t)i * stride_w * 4, rows + (size_t)i * row_bytes, (size_t)used);
+  HIPCHK(hipMemcpyAsync(h.d_bits, hs, bits_bytes, hipMemcpyHostToDevice, c->st));
+  long long* d_cnt = static_cast<long long*>(c->d_stage);
+  HIPCHK(launch_bed_stats(h.d_bits, stride_w, (int)n, nsamp, d_cnt, h.d_lut, h.d_msd, c->st));
+  CHK(stream_wait(c));   // the bits have left the staging buffer
+  HIPCHK(hipMemcpyAsync(c->h_stage, d_cnt, cnt_bytes, hipMemcpyDeviceToHost, c->st));
+  CHK(stream_wait(c));
+  const long long* hc = static_cast<const long long*>(c->h_stage);
+  int64_t nbad = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const long long c0 = hc[4 * i], c2 = hc[4 * i + 2], c3 = hc[4 * i + 3];
+    const long long nobs = c0 + c2 + c3, S1 = 2 * c0 + c2, S2 = 4 * c0 + c2;
+    if (nobs == 0 || nobs * S2 - S1 * S1 == 0) ++nbad;
+    for (int k = 0; k < 4; ++k) counts_out[4 * i + k] = (int64_t)hc[4 * i + k];
+  }
+  if (nbad)   // nothing registered: the coupling stays as it was
+    return fail(c, SGV_ERR_STATE, "sgv_geno_coupling: coupling %d has %lld marker(s) without LD "
+                "(monomorphic or unobserved)", gb, (long long)nbad);
+  HIPCHK(hipMemsetAsync(guard.d_C, 0, c_bytes, c->st));
+  HIPCHK(launch_bed_cross(h.d_bits, stride_w, h.d_lut, nr, nc, nsamp, window, c->ld_bits,
+                          guard.d_C, c->st));
+  HIPCHK(hipMemcpyAsync(c->h_stage, guard.d_C, c_bytes, hipMemcpyDeviceToHost, c->st));
+  CHK(stream_wait(c));
+  return ld_set_coupling(c, "sgv_geno_coupling", ld, gb, nr, nc,
+                         static_cast<const double*>(c->h_stage));
+}
+
 extern "C" int sgv_geno_r(sgv_ctx* c, int k, const double* y) {
   ENTER(c);
   if (k < 0 || k >= c->K || !y) return fail(c, SGV_ERR_ARG, "sgv_geno_r: bad arguments");

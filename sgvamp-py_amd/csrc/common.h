@@ -721,6 +721,17 @@ hipError_t launch_bed_stats(const uint32_t* d_bits, int64_t stride_w, int n, int
 hipError_t launch_bed_syrk(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int n,
                            int nsamp, void* d_R, int64_t lda, int packed, const int64_t* d_poff,
                            const int64_t* d_pw, int bits, hipStream_t st);
+// windowed R: only entries with |i - j| <= window, into a zeroed packed block of
+// stored extent ext (0: the packed triangle); entry for entry launch_bed_syrk's
+hipError_t launch_bed_syrk_band(const uint32_t* d_bits, int64_t stride_w, const double* d_lut,
+                                int n, int nsamp, int64_t window, int64_t ext, void* d_R,
+                                const int64_t* d_poff, const int64_t* d_pw, int bits,
+                                hipStream_t st);
+// C = G_tail G_head^T (nr x nc doubles, zeroed by the caller) of nr + nc staged
+// rows, entries (a, c) with c + nr - a <= window; bits == 32: rounded once to f32
+hipError_t launch_bed_cross(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int nr,
+                            int nc, int nsamp, int64_t window, int bits, double* d_C,
+                            hipStream_t st);
 hipError_t launch_bed_row_dot(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int n,
                               int nsamp, const double* d_y, double* d_out, hipStream_t st);
 hipError_t launch_bed_g_accum(const uint32_t* d_bits, int64_t stride_w, const double* d_msd, int n,

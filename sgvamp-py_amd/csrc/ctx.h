@@ -459,6 +459,7 @@ int gather_r1(sgv_ctx* c);
 void free_plan(LdPlan& p);
 void free_block(LdBlock& lb);
 int ld_alloc(sgv_ctx* c, int ld, int b, int fmt, int64_t ext = 0);
+int ld_set_coupling(sgv_ctx* c, const char* who, int ld, int gb, int nr, int nc, const double* C);
 int grow(sgv_ctx* c, double** buf, size_t* cap, size_t need);
 int ensure_plan(sgv_ctx* c, int ld);
 const int* ld_parts(sgv_ctx* c, int ld);

@@ -191,6 +191,160 @@ hipError_t launch_bed_syrk(const uint32_t* d_bits, int64_t stride_w, const doubl
   return hipGetLastError();
 }
 
+// k_bed_syrk's contraction of one 64 x 64 tile, for the windowed kernels: rows
+// ra0 .. ra0 + 63 of (bits_a, lut_a) against rows rb0 .. rb0 + 63 of (bits_b,
+// lut_b); rows >= na / nb give 0.  acc[a][b] is output (ra0 + ty + 16 a, rb0 + tx
+// + 16 b): the same sample-sequential fma chain, k ascending, one accumulator per
+// output, so an entry is the same double whichever kernel forms it.
+__device__ __forceinline__ void bed_tile(const uint8_t* __restrict__ bits_a,
+                                         const double* __restrict__ lut_a, int ra0, int na,
+                                         const uint8_t* __restrict__ bits_b,
+                                         const double* __restrict__ lut_b, int rb0, int nb,
+                                         int64_t stride_b, int nsamp, double (&acc)[4][4]) {
+  __shared__ double As[16][64 + 2];
+  __shared__ double Bs[16][64 + 2];
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int lr = threadIdx.x >> 2, lq = threadIdx.x & 3;   // loader: tile row, byte of the word
+  const bool va = ra0 + lr < na, vb = rb0 + lr < nb;
+  double a0 = 0.0, a2 = 0.0, a3 = 0.0, b0 = 0.0, b2 = 0.0, b3 = 0.0;
+  if (va) {
+    const double* l = lut_a + 4 * (int64_t)(ra0 + lr);
+    a0 = l[0], a2 = l[2], a3 = l[3];
+  }
+  if (vb) {
+    const double* l = lut_b + 4 * (int64_t)(rb0 + lr);
+    b0 = l[0], b2 = l[2], b3 = l[3];
+  }
+  const uint8_t* pa = bits_a + (int64_t)(va ? ra0 + lr : 0) * stride_b + lq;
+  const uint8_t* pb = bits_b + (int64_t)(vb ? rb0 + lr : 0) * stride_b + lq;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+  const int kpad = (nsamp + 15) / 16 * 16;   // == 4 stride_b: every byte read is inside the row
+  unsigned ba = pa[0], bb = pb[0];
+  for (int k0 = 0; k0 < kpad; k0 += 16) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int kk = 4 * lq + e;
+      const bool in = k0 + kk < nsamp;
+      As[kk][lr] = in ? bed_pick((ba >> (2 * e)) & 3, a0, a2, a3) : 0.0;
+      Bs[kk][lr] = in ? bed_pick((bb >> (2 * e)) & 3, b0, b2, b3) : 0.0;
+    }
+    if (k0 + 16 < kpad) {
+      ba = pa[(k0 >> 2) + 4];
+      bb = pb[(k0 >> 2) + 4];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+      double av[4], bv[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) av[a] = As[kk][ty + 16 * a];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) bv[b] = Bs[kk][tx + 16 * b];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_fma(av[a], bv[b], acc[a][b]);
+    }
+    __syncthreads();
+  }
+}
+
+// Windowed R (include/sgvamp_hip.h, "windowed genotype LD"): k_bed_syrk over the
+// tiles of the band only.  Grid (column tiles a row tile reaches within W) x
+// (row tiles), tj = ti + blockIdx.x.  Entry (i, j), j >= i, is stored iff j - i
+// <= W; everything else keeps the zero the caller's memset left.  (j, i) is
+// stored too where it lies in the panel's diagonal 256 x 256 block, which the
+// packed layout keeps in full.  ext: the packed band's stored extent (0: the
+// packed triangle); a panel starting at row r0 holds columns r0 .. r0 +
+// min(n - r0, ext) - 1, which sym_addr does not know.
+template <class T>
+__global__ __launch_bounds__(256) void k_bed_syrk_band(const uint8_t* __restrict__ bits,
+                                                       int64_t stride_b,
+                                                       const double* __restrict__ lut, int n,
+                                                       int nsamp, int64_t W, int64_t ext,
+                                                       T* __restrict__ R,
+                                                       const int64_t* __restrict__ poff,
+                                                       const int64_t* __restrict__ pw) {
+  const int ti = blockIdx.y;
+  const int64_t tj = (int64_t)ti + blockIdx.x;
+  const int i0 = ti * 64;
+  // nearest pair of the tile: (i0 + 63, j0); no in-band entry, or no column: nothing to load
+  if (tj * 64 >= n || tj * 64 - (i0 + 63) > W) return;
+  const int j0 = (int)tj * 64;
+  double acc[4][4];
+  bed_tile(bits, lut, i0, n, bits, lut, j0, n, stride_b, nsamp, acc);
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int i = i0 + ty + 16 * a, j = j0 + tx + 16 * b;
+      if (i >= n || j >= n || j < i || (int64_t)j - i > W) continue;
+      const int r0 = i / SYM_H * SYM_H;
+      const int64_t cols = ext > 0 && ext < n - r0 ? ext : n - r0;   // the panel's stored columns
+      if (j - r0 >= cols) continue;        // cannot happen: j <= i + W < r0 + 256 + W <= r0 + ext
+      *sym_addr(R, poff, pw, i, j) = (T)acc[a][b];
+      if (j != i && j < r0 + SYM_H) *sym_addr(R, poff, pw, j, i) = (T)acc[a][b];
+    }
+}
+
+hipError_t launch_bed_syrk_band(const uint32_t* d_bits, int64_t stride_w, const double* d_lut,
+                                int n, int nsamp, int64_t window, int64_t ext, void* d_R,
+                                const int64_t* d_poff, const int64_t* d_pw, int bits,
+                                hipStream_t st) {
+  const int64_t nt = ((int64_t)n + 63) / 64;
+  if (window < 1 || nt > 65535) return hipErrorInvalidValue;
+  // the farthest column of row tile ti is 64 ti + 63 + W: tile ti + (63 + W) / 64
+  const int64_t nx = std::min<int64_t>(nt, (63 + window) / 64 + 1);
+  const uint8_t* by = reinterpret_cast<const uint8_t*>(d_bits);
+  if (bits == 32)
+    hipLaunchKernelGGL(k_bed_syrk_band<float>, dim3((unsigned)nx, (unsigned)nt), dim3(256), 0, st,
+                       by, stride_w * 4, d_lut, n, nsamp, window, ext, (float*)d_R, d_poff, d_pw);
+  else
+    hipLaunchKernelGGL(k_bed_syrk_band<double>, dim3((unsigned)nx, (unsigned)nt), dim3(256), 0, st,
+                       by, stride_w * 4, d_lut, n, nsamp, window, ext, (double*)d_R, d_poff, d_pw);
+  return hipGetLastError();
+}
+
+// The band's corner between two pieces: C = G_tail G_head^T (nr x nc, row major)
+// from one staged row set, the tail's nr rows first, then the head's nc.  Entry
+// (a, c) couples markers c + nr - a apart and is stored iff that is <= W; C was
+// zeroed by the caller.  f32: the entry is rounded once to f32 (what the uncut
+// f32 band stores) and kept as the double of that float.
+__global__ __launch_bounds__(256) void k_bed_cross(const uint8_t* __restrict__ bits,
+                                                   int64_t stride_b,
+                                                   const double* __restrict__ lut, int nr, int nc,
+                                                   int nsamp, int64_t W, int f32,
+                                                   double* __restrict__ C) {
+  const int a0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+  if (a0 >= nr || c0 >= nc || (int64_t)c0 + nr - (a0 + 63) > W) return;   // nearest pair: (a0 + 63, c0)
+  double acc[4][4];
+  bed_tile(bits, lut, a0, nr, bits + (int64_t)nr * stride_b, lut + 4 * (int64_t)nr, c0, nc,
+           stride_b, nsamp, acc);
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int ia = a0 + ty + 16 * a, ic = c0 + tx + 16 * b;
+      if (ia >= nr || ic >= nc || (int64_t)ic + nr - ia > W) continue;
+      C[(int64_t)ia * nc + ic] = f32 ? (double)(float)acc[a][b] : acc[a][b];
+    }
+}
+
+hipError_t launch_bed_cross(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int nr,
+                            int nc, int nsamp, int64_t window, int bits, double* d_C,
+                            hipStream_t st) {
+  if (nr < 1 || nc < 1 || window < 1 || (nr + 63) / 64 > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_bed_cross, dim3((nc + 63) / 64, (nr + 63) / 64), dim3(256), 0, st,
+                     reinterpret_cast<const uint8_t*>(d_bits), stride_w * 4, d_lut, nr, nc, nsamp,
+                     window, bits == 32 ? 1 : 0, d_C);
+  return hipGetLastError();
+}
+
 // out[i] = sum_n t_i[code_in] y[n]; one wave per marker, k_row_dot's lane order
 __global__ __launch_bounds__(256) void k_bed_row_dot(const uint8_t* __restrict__ bits,
                                                      int64_t stride_b,

@@ -1085,16 +1085,16 @@ extern "C" int sgv_ld_block_format(sgv_ctx* c, int ld, int b, int* fmt_out) {
   return SGV_OK;
 }
 
-extern "C" int sgv_set_ld_coupling(sgv_ctx* c, int ld, int gb, int nr, int nc, const double* C) {
-  ENTER(c);
+// registers coupling gb of LD matrix ld (sgv_set_ld_coupling, sgv_geno_coupling):
+// C^T where this rank owns piece gb, C where it owns gb + 1; the plan is rebuilt
+int ld_set_coupling(sgv_ctx* c, const char* who, int ld, int gb, int nr, int nc, const double* C){
   if (ld < 0 || ld >= c->nld || gb < 0 || gb + 1 >= c->nblk_global || nr < 1 || nc < 1)
-    return fail(c, SGV_ERR_ARG, "sgv_set_ld_coupling: bad arguments (ld %d, gb %d, %d x %d)", ld,
-                gb, nr, nc);
+    return fail(c, SGV_ERR_ARG, "%s: bad arguments (ld %d, gb %d, %d x %d)", who, ld, gb, nr, nc);
   const int ba = gb - c->blk0, bb = gb + 1 - c->blk0;
   const bool la = ba >= 0 && ba < c->nblk, lb = bb >= 0 && bb < c->nblk;
   if ((la && nr > c->bn[ba]) || (lb && nc > c->bn[bb]))
-    return fail(c, SGV_ERR_ARG, "sgv_set_ld_coupling: %d x %d exceeds the pieces", nr, nc);
-  if ((la || lb) && !C) return fail(c, SGV_ERR_ARG, "sgv_set_ld_coupling: C is null");
+    return fail(c, SGV_ERR_ARG, "%s: %d x %d exceeds the pieces", who, nr, nc);
+  if ((la || lb) && !C) return fail(c, SGV_ERR_ARG, "%s: C is null", who);
   std::vector<LdCoupling>& cv = c->cpl[ld];
   auto it = std::find_if(cv.begin(), cv.end(), [&](const LdCoupling& q) { return q.gb == gb; });
   if (it == cv.end()) {
@@ -1122,6 +1122,11 @@ extern "C" int sgv_set_ld_coupling(sgv_ctx* c, int ld, int gb, int nr, int nc, c
   std::sort(cv.begin(), cv.end(), [](const LdCoupling& a, const LdCoupling& b) { return a.gb < b.gb; });
   c->plan[ld].valid = false;
   return SGV_OK;
+}
+
+extern "C" int sgv_set_ld_coupling(sgv_ctx* c, int ld, int gb, int nr, int nc, const double* C) {
+  ENTER(c);
+  return ld_set_coupling(c, "sgv_set_ld_coupling", ld, gb, nr, nc, C);
 }
 
 extern "C" int sgv_ld_stored_bytes(sgv_ctx* c, int ld, double* out) {

@@ -246,6 +246,42 @@ class Engine:
             return
         self.ctx.sgv_geno_ld(int(ld), b_global - self.b0)
 
+    def geno_ld_band(self, ld, b_global, window):
+        """Windowed R_b of the staged genotypes (entries with |i - j| <= window, 0
+        elsewhere) into LD matrix ld as a packed band (this rank's block; the
+        engine's precision; packing must be on)."""
+        if not (self.b0 <= b_global < self.b1):
+            return
+        self.ctx.sgv_geno_ld_band(int(ld), b_global - self.b0, int(window))
+
+    def geno_coupling(self, ld, gb, nr, nc, rows, nsamp, window, check=None):
+        """Coupling between band pieces gb and gb + 1 (global indices) of LD matrix
+        ld from genotypes: rows = a callable returning, or an array of, the (nr +
+        nc, >= ceil(nsamp / 4)) uint8 .bed rows of gb's last nr markers, then gb +
+        1's first nc; read only where this rank owns one of the two pieces.  Called
+        on every rank for every coupling.  Returns the rows' (nr + nc, 4) code
+        counts, or None.  check(counts), if given, runs before the library's error
+        for rows without LD is raised, so the caller can name them."""
+        own = self.b0 <= gb < self.b1 or self.b0 <= gb + 1 < self.b1
+        n = int(nr) + int(nc)
+        counts, rp, cp, nb = None, None, None, 0
+        if own:
+            rows = np.asarray(rows() if callable(rows) else rows)
+            if rows.dtype != np.uint8 or rows.ndim != 2 or rows.shape[0] != n \
+                    or rows.shape[1] < (int(nsamp) + 3) // 4 or int(nsamp) < 1:
+                raise ValueError("genotype rows of coupling %d: %s %s, expected uint8 (%d, >= %d)"
+                                 % (gb, rows.dtype, rows.shape, n, (int(nsamp) + 3) // 4))
+            rows = np.ascontiguousarray(rows)
+            counts = np.zeros((n, 4), dtype=np.int64)
+            rp, cp, nb = rows.ctypes.data_as(hb._c_u8_p), counts.ctypes.data_as(hb._c_i64_p), \
+                int(rows.shape[1])
+        rc = self.ctx.lib.sgv_geno_coupling(self.ctx.h, int(ld), int(gb), int(nr), int(nc), rp, nb,
+                                            int(nsamp), int(window), cp)
+        if rc != hb.SGV_OK and check is not None and counts is not None:
+            check(counts)
+        self.ctx.check(rc, "sgv_geno_coupling")
+        return counts
+
     def geno_r(self, k, y):
         """r_k = G y over this rank's blocks (get_vector(VEC_R, k) reads it)."""
         y = np.ascontiguousarray(y, dtype=np.float64).ravel()

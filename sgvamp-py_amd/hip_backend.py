@@ -75,6 +75,9 @@ _SIGS = {
     "sgv_synth_r": [_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, _c_dbl_p],
     "sgv_geno_set_block": [_vp, ctypes.c_int, _c_u8_p, ctypes.c_int64, ctypes.c_int, _c_i64_p],
     "sgv_geno_ld": [_vp, ctypes.c_int, ctypes.c_int],
+    "sgv_geno_ld_band": [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64],
+    "sgv_geno_coupling": [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_u8_p,
+                          ctypes.c_int64, ctypes.c_int, ctypes.c_int64, _c_i64_p],
     "sgv_geno_r": [_vp, ctypes.c_int, _c_dbl_p],
     "sgv_geno_g": [_vp, _c_dbl_p, _c_dbl_p],
     "sgv_geno_clear": [_vp],

@@ -302,11 +302,21 @@ class BedLD(BlockLD):
     product: slow, for checks and for regroup(), which on the same partition
     returns this object and on a coarser one a plain BlockLD whose blocks are
     assembled on the host from block() -- the slow path).  ``select``: panel rows in marker
-    order (default: the panel's own order)."""
+    order (default: the panel's own order).
+
+    ``window`` (markers of that order, >= 1; None: none): inside each block only
+    the entries with |i - j| <= window are kept, everything else is exactly 0
+    (include/sgvamp_hip.h, "windowed genotype LD").  The block is then a symmetric
+    band of width min(window, n_b - 1): upload() forms it on the device as a
+    packed band (the engine's packing must be on), band_cuts() may cut it into
+    pieces, and pieces() gives those pieces' couplings as GenoCoupling objects,
+    formed on the device from the 2 * window rows next to each cut.  Truncating
+    LD to a window does not preserve positive semi-definiteness; the ridge ``s``
+    is the remedy."""
 
     uses_geno = True
 
-    def __init__(self, panel, block_sizes, select=None, s=0.0):
+    def __init__(self, panel, block_sizes, select=None, s=0.0, window=None):
         sizes = [int(b) for b in block_sizes]
         super().__init__(block_sizes=sizes, loader=self._host_block, s=s)
         self.panel = panel
@@ -316,22 +326,25 @@ class BedLD(BlockLD):
             raise ValueError("LD block sizes sum to %d, the panel selection has %d markers"
                              % (sum(sizes), m))
         self._offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        self.window = check_ld_window(window)
 
     def _index(self, b):
         o0, o1 = int(self._offs[b]), int(self._offs[b + 1])
         return np.arange(o0, o1) if self.select is None else self.select[o0:o1]
 
-    def rows(self, b):
-        """The block's packed rows, (n_b, ceil(N / 4)) uint8."""
-        ix = self._index(b)
+    def _read(self, ix):
         if len(ix) and np.all(np.diff(ix) == 1):   # one contiguous read of the file
             return np.ascontiguousarray(self.panel.rows[int(ix[0]):int(ix[-1]) + 1])
         return np.ascontiguousarray(self.panel.rows[ix])
 
+    def rows(self, b):
+        """The block's packed rows, (n_b, ceil(N / 4)) uint8."""
+        return self._read(self._index(b))
+
     def variant_ids(self, b):
         return [self.panel.ids[i] for i in self._index(b)]
 
-    def check_counts(self, b, counts):
+    def check_counts(self, b, counts, ids=None, what=None):
         """ValueError naming the block's markers that have no LD (no observed
         sample, or one value among them), from their code counts."""
         c = np.asarray(counts, dtype=np.int64)
@@ -340,18 +353,18 @@ class BedLD(BlockLD):
         s2 = 4 * c[:, 0] + c[:, 2]
         bad = np.flatnonzero((nobs == 0) | (nobs * s2 - s1 * s1 == 0))
         if len(bad):
-            ids = self.variant_ids(b)
-            raise ValueError("%d marker(s) of LD block %d have no LD (monomorphic among their "
+            ids = self.variant_ids(b) if ids is None else ids
+            raise ValueError("%d marker(s) of %s have no LD (monomorphic among their "
                              "observed samples, or all missing): %s%s"
-                             % (len(bad), b, ", ".join(str(ids[i]) for i in bad[:5]),
+                             % (len(bad), what or "LD block %d" % b,
+                                ", ".join(str(ids[i]) for i in bad[:5]),
                                 ", ..." if len(bad) > 5 else ""))
 
-    def standardised(self, b):
-        """G_b (n_b, N) on the host, and the code counts."""
+    def _standardise(self, rows, check):
         N = self.panel.N
-        codes = bed_codes(self.rows(b), N)
+        codes = bed_codes(rows, N)
         counts = np.stack([(codes == k).sum(axis=1) for k in range(4)], axis=1).astype(np.int64)
-        self.check_counts(b, counts)
+        check(counts)
         nobs = counts[:, 0] + counts[:, 2] + counts[:, 3]
         s1 = 2 * counts[:, 0] + counts[:, 2]
         s2 = 4 * counts[:, 0] + counts[:, 2]
@@ -363,30 +376,150 @@ class BedLD(BlockLD):
         G[codes == 1] = 0.0
         return G, counts
 
+    def standardised(self, b):
+        """G_b (n_b, N) on the host, and the code counts."""
+        return self._standardise(self.rows(b), lambda counts: self.check_counts(b, counts))
+
     def _host_block(self, b):
         G, _ = self.standardised(b)
-        return G @ G.T
+        R = G @ G.T
+        if self.window is not None:
+            i = np.arange(R.shape[0])
+            R[np.abs(i[:, None] - i[None, :]) > self.window] = 0.0
+        return R
 
     def block_csr(self, b):
         return None
 
     def band_width(self, b):
-        return None
+        """min(window, n_b - 1) of a windowed source; None (a dense block) without."""
+        return None if self.window is None else min(self.window, self.block_sizes[b] - 1)
+
+    def symmetric(self, b, A=None):
+        return True if self.window is not None else super().symmetric(b, A)
 
     def upload(self, eng, ld, b, packed=True):
         """Stage block b's rows on the engine and form R_b there (this rank's
         blocks only; `packed` is the engine's own setting)."""
+        if self.window is not None and not packed:
+            raise ValueError("windowed genotype LD (window %d) is stored as a packed band: "
+                             "it needs LD packing on" % self.window)
         if not (eng.b0 <= b < eng.b1):
             return
         counts = eng.geno_set_block(b, self.rows(b), self.panel.N)
         self.check_counts(b, counts)
-        eng.geno_ld(ld, b)
+        if self.window is not None:
+            eng.geno_ld_band(ld, b, self.window)
+        else:
+            eng.geno_ld(ld, b)
+
+    def pieces(self, cuts):
+        """The same windowed matrix on a finer partition that cuts blocks into
+        pieces (sgvamp.BlockLD.pieces): a BedLD of the same panel, order and window
+        on the piece partition -- so a rank reads only its own pieces' rows -- and
+        {gb: GenoCoupling} between consecutive pieces of one block, nr = min(bw,
+        n_gb), nc = min(bw, n_gb+1), bw the block's band width.  A coupling holds
+        the panel rows of its halo, not a matrix."""
+        sizes = [int(n) for ps in cuts for n in ps]
+        if len(sizes) == len(self.block_sizes):
+            return self, {}
+        if self.window is None:
+            raise ValueError("a genotype LD source without a window has dense blocks: no pieces")
+        L = BedLD(self.panel, sizes, select=self.select, s=self.s, window=self.window)
+        couplings = {}
+        k = 0
+        for b, ps in enumerate(cuts):
+            if len(ps) > 1:
+                bw = max(1, self.band_width(b))
+                o = int(self._offs[b])
+                for i in range(len(ps) - 1):
+                    cut = o + int(ps[i])
+                    nr, nc = min(bw, int(ps[i])), min(bw, int(ps[i + 1]))
+                    m = np.arange(cut - nr, cut + nc)
+                    couplings[k + i] = GenoCoupling(
+                        L, nr, nc, m if self.select is None else self.select[m])
+                    o = cut
+            k += len(ps)
+        return L, couplings
+
+    def regroup(self, sizes):
+        """On the same partition this object.  On a coarser one the slow path: a
+        plain BlockLD whose blocks are assembled on the host from block() (masked to
+        the window inside each original block), each refused where it exceeds the
+        dense-block limit."""
+        if list(sizes) == list(self.block_sizes):
+            return self
+        L = super().regroup(sizes)
+        if self.window is not None:
+            from sgvamp import _dense_guard
+
+            assemble = L._loader
+
+            def load(b):
+                _dense_guard(L.block_sizes[b], "genotype LD blocks regrouped on the host")
+                return assemble(b)
+
+            L._loader = load
+        return L
 
 
-def load_bed_ld(path, s, block_size=None, blocks_file=None, variants=None):
+class GenoCoupling:
+    """Coupling between band pieces gb and gb + 1 of a windowed BedLD, kept as the
+    panel rows of its halo: ``index`` = the panel rows of gb's last nr markers,
+    then of gb + 1's first nc.  C = G_tail G_head^T masked to the window is formed
+    on the device (upload); host() is the same in NumPy, for checks."""
+
+    def __init__(self, ld, nr, nc, index):
+        self.ld, self.nr, self.nc = ld, int(nr), int(nc)
+        self.index = np.asarray(index, dtype=np.int64)
+        if len(self.index) != self.nr + self.nc:
+            raise ValueError("a %d x %d coupling needs %d halo rows, not %d"
+                             % (self.nr, self.nc, self.nr + self.nc, len(self.index)))
+
+    def rows(self):
+        """The halo's packed rows, (nr + nc, ceil(N / 4)) uint8."""
+        return self.ld._read(self.index)
+
+    def variant_ids(self):
+        return [self.ld.panel.ids[i] for i in self.index]
+
+    def _check(self, gb, counts):
+        self.ld.check_counts(None, counts, ids=self.variant_ids(),
+                             what="the coupling between LD band pieces %d and %d" % (gb, gb + 1))
+
+    def host(self, gb=0):
+        G, _ = self.ld._standardise(self.rows(), lambda counts: self._check(gb, counts))
+        C = G[:self.nr] @ G[self.nr:].T
+        a, c = np.arange(self.nr)[:, None], np.arange(self.nc)[None, :]
+        C[c + self.nr - a > self.ld.window] = 0.0
+        return C
+
+    def upload(self, eng, ld, gb):
+        """Register the coupling on the engine (every rank, every coupling: the
+        rows are read only where the rank owns one of the two pieces)."""
+        eng.geno_coupling(ld, gb, self.nr, self.nc, self.rows, self.ld.panel.N, self.ld.window,
+                          check=lambda counts: self._check(gb, counts))
+
+
+def check_ld_window(window):
+    """An LD window as a positive int (None: no window); ValueError otherwise."""
+    if window is None:
+        return None
+    try:
+        w = int(window)
+        ok = w >= 1 and w == window
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("the LD window must be a positive number of markers, not %r" % (window,))
+    return w
+
+
+def load_bed_ld(path, s, block_size=None, blocks_file=None, variants=None, window=None):
     """A .bed panel as a BedLD: blocks of block_size markers (the last shorter) or
     the sizes listed one per line in blocks_file; variants: the marker order as
-    variant ids (default: the panel's own)."""
+    variant ids (default: the panel's own); window: keep only LD within that many
+    markers of the diagonal, as packed bands (BedLD)."""
     panel = read_bed(path)
     select = None if variants is None else panel.index_of(list(variants))
     M = panel.M if select is None else len(select)
@@ -398,4 +531,4 @@ def load_bed_ld(path, s, block_size=None, blocks_file=None, variants=None):
                              % (blocks_file, sum(sizes), M))
     else:
         sizes = equal_blocks(M, block_size)
-    return BedLD(panel, sizes, select=select, s=s)
+    return BedLD(panel, sizes, select=select, s=s, window=window)

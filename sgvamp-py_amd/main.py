@@ -24,7 +24,13 @@ Same flags, defaults, validation messages, log lines and output files
   the last shorter) or --ld-blocks FILE (one size per line); exactly one of the
   two is required.  With --bim-files the panel's rows are matched to the merged
   marker order by variant id (ids only, no allele reconciliation, as the
-  reference matches); without, the panel's own order is used.
+  reference matches); without, the panel's own order is used.  --ld-window W
+  (a positive number of markers of that order) keeps only the LD within W
+  markers of the diagonal inside each block: the blocks -- the chromosomes or
+  segments the window does not cross -- are then formed as packed bands on the
+  device, cut into coupled pieces like any windowed LD (sgvamp.BAND_PIECE).
+  Truncated LD need not be positive semi-definite (as with PLINK's --ld-window);
+  --s is the remedy.  It needs packed LD storage (--ld-packing on, the default).
 """
 import argparse
 import logging
@@ -87,6 +93,10 @@ def build_parser():
                         help="With a .bed LD source: LD blocks of this many markers (the last one shorter)")
     parser.add_argument("--ld-blocks", default=None,
                         help="With a .bed LD source: file listing the LD block sizes, one per line")
+    parser.add_argument("--ld-window", default=None,
+                        help="With a .bed LD source: keep only the LD between markers at most this many markers apart (in the run's marker order, inside each LD block) and store the blocks as packed bands formed on the device; a window does not preserve positive semi-definiteness, --s is the remedy")
+    parser.add_argument("--ld-packing", choices=["on", "off"], default="on",
+                        help="Packed storage of symmetric LD blocks (on, the default) or full dense squares (off)")
     return parser
 
 
@@ -108,6 +118,17 @@ def check_bed_flags(parser, args):
             ok = False
         if not ok:
             parser.error("--ld-block-size must be a positive integer, not %r" % (args.ld_block_size,))
+    if args.ld_window is not None:
+        if not bed:
+            parser.error("--ld-window applies to a .bed LD source only")
+        try:
+            ok = int(args.ld_window) >= 1
+        except ValueError:
+            ok = False
+        if not ok:
+            parser.error("--ld-window must be a positive integer (markers), not %r" % (args.ld_window,))
+        if args.ld_packing == "off":
+            parser.error("--ld-window stores packed bands: it cannot be combined with --ld-packing off")
 
 
 def pip_threshold_arg(text):
@@ -236,7 +257,8 @@ def main(argv=None):
                 if p.endswith(".bed"):   # genotypes: the blocks are formed on the device
                     by_path[p] = load_bed_ld(
                         p, s, block_size=args.ld_block_size, blocks_file=args.ld_blocks,
-                        variants=bim_ref if bim_fpaths is not None else None)
+                        variants=bim_ref if bim_fpaths is not None else None,
+                        window=None if args.ld_window is None else int(args.ld_window))
                 else:
                     by_path[p] = load_ld(p, s)
             lds.append(by_path[p])
@@ -261,7 +283,7 @@ def main(argv=None):
                prior_vars=prior_vars_list, prior_probs=prior_probs_list, out_dir=out_dir,
                out_name=out_name, comm=comm, seed=seed,
                device=None if args.device is None else int(args.device),
-               ld_precision=args.ld_precision,
+               ld_precision=args.ld_precision, ld_packing=args.ld_packing == "on",
                posterior=None if args.posterior == "none" else args.posterior,
                pip_threshold=args.pip_threshold)
     if rank == 0:

@@ -514,8 +514,11 @@ class VAMP:
             for b in range(eng.b0, eng.b1):
                 L.upload(eng, l, b, packed=self.ld_packing)
             for gb in sorted(couplings[l]):   # every rank, every coupling (collective)
-                nr, nc, C = couplings[l][gb]
-                eng.set_ld_coupling(l, gb, nr, nc, C)
+                cp = couplings[l][gb]
+                if isinstance(cp, tuple):     # (nr, nc, C): a matrix sliced on the host
+                    eng.set_ld_coupling(l, gb, *cp)
+                else:                         # genotypes: formed on the device from the halo's rows
+                    cp.upload(eng, l, gb)
         if any(getattr(L, "uses_geno", False) for L in uniq):
             eng.geno_clear()   # the blocks are stored: the staged genotype rows can go
         eng.update_cg_exact()   # the run's CG column sets from the bytes stored (collective)
