@@ -225,6 +225,10 @@ int sgv_set_ridge(sgv_ctx* ctx, double s);
 /* Cohort sample size N_k (src/main.py:83-85; used by gamw learning :352,363). */
 int sgv_set_cohort_n(sgv_ctx* ctx, int k, double N);
 
+/* SGV_VEC_XHAT2 / SGV_VEC_SIG2U set the next LMMSE step's warm start: R_s x0 of a
+ * non-zero vector is re-derived by one LD pass in that step; an all-zero vector
+ * makes the column cold (as after sgv_reset_solver) and its stored R_s x0 is
+ * zeroed with it. */
 int sgv_set_vector(sgv_ctx* ctx, int which, int k, const double* host_local);
 int sgv_get_vector(sgv_ctx* ctx, int which, int k, double* host_local);
 

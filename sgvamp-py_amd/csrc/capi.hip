@@ -595,6 +595,13 @@ extern "C" int sgv_set_vector(sgv_ctx* c, int which, int k, const double* host) 
     const int col = 2 * k + (which == SGV_VEC_SIG2U);
     c->xnz[col] = host_any(host, c->Mloc);
     c->rx0_valid[col] = 0;
+    // a zeroed column is cold: no warm-start pass re-derives its R_s x, yet the
+    // carried recurrence adds to RX0 (k_cg_xr) and the damping saves it
+    // (k_lmmse_init), so R_s 0 = 0 is stored with it
+    if (!c->xnz[col]) {
+      HIPCHK(hipMemsetAsync(c->RX0[col], 0, sizeof(double) * (size_t)c->Mpad, c->st));
+      CHK(stream_wait(c));
+    }
   }
   return SGV_OK;
 }

@@ -914,10 +914,11 @@ static int lmmse_group(sgv_ctx* c, int g0, int Kg, const double* gamw, const dou
   double tot[2 * MAXC];
   const bool dev_init = c->cg_pipe;   // CG prologue on the device: no host round trip
   // with a communicator and one LD matrix for the group's columns: the prologue's
-  // sums share iteration 0's exchange (cg_loop_dev, CgMerge0)
+  // sums share iteration 0's exchange (cg_loop_dev, CgMerge0); without an
+  // iteration 0 (cg_maxit == 0) nothing would reduce them or set the CG state
   bool one_ld = true;
   for (int k = 1; k < K; ++k) one_ld &= c->ld_of[g0 + k] == c->ld_of[g0];
-  const bool merge0 = dev_init && (c->comm || c->host_ag) && one_ld;
+  const bool merge0 = dev_init && (c->comm || c->host_ag) && one_ld && cg_maxit > 0;
   if (merge0) CHK(grow(c, &c->d_part2, &c->part2_cap, (size_t)c->nch * 2 * MAXC));
   HIPCHK(launch_lmmse_init(c->d_ch, c->nch, ia, merge0 ? c->d_part2 : c->d_part, c->st));
   CgMerge0 mg;
