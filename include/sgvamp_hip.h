@@ -39,8 +39,9 @@ extern "C" {
 /* ABI revision of this header.  2: sgv_timers / sgv_exchange_stats take the
  * caller's buffer length (cap), sgv_comm_info added.  An integrator checks
  * sgv_abi_version() == SGV_ABI_VERSION before binding the rest.  Entry points
- * added since (sgv_posterior, the sgv_geno_* family) change no existing
- * signature or layout and leave the revision at 2. */
+ * added since (sgv_posterior, the sgv_geno_* family, sgv_ld_pass_form and
+ * sgv_pass_form_model) change no existing signature or layout and leave the
+ * revision at 2. */
 #define SGV_ABI_VERSION 2
 int sgv_abi_version(void);
 
@@ -186,7 +187,8 @@ int sgv_ld_block_format(sgv_ctx* ctx, int ld, int blk_local, int* fmt_out);
  * wide forms are f64-only; the band walks have float instances, but measured
  * 1.26-1.33x the strips' time on an f32 band at 3-8 columns, so a windowed-LD
  * matrix stored as f32 stays on the strips too and walks only with SGV_AB=1
- * SGV_F32_WALK=1: DESIGN.md 4.4); a block's sums are a function of the
+ * SGV_F32_WALK=1: DESIGN.md 4.4; the decision is pass_form's, csrc/pass_form.cpp,
+ * and sgv_ld_pass_form reports it); a block's sums are a function of the
  * block alone, within 1e-12 of the f64 product of the stored values (with
  * SGV_AB=1 SGV_F32_FORM=1, the 8-byte load form, bitwise the f64 strips').
  * Measured per pass against f64: 0.53-0.57x at 2-4 columns, 0.67-0.74x at 8,
@@ -617,6 +619,83 @@ int sgv_exchange_probe(sgv_ctx* ctx, int reps, double* us_out);
  * runs the cheaper (sgv_exchange_stats out[3], out[8..10]). */
 int sgv_em_cost_model(double cohort_markers, int nranks, double latency_us, double steps,
                       double* out2);
+
+/* The kernel form the next pass of ncol columns (1..16) over LD matrix ld would
+ * take, as ints: the decision of csrc/pass_form.cpp on this context's plan,
+ * sgv_set_mfma_min and the pass switches as a pass reads them (DESIGN.md
+ * Appendix B).  Builds the plan's tables if a block changed, as a pass would;
+ * launches nothing else.  Writes min(cap, SGV_PF_N) values:
+ * form[SGV_PF_KIND]: how the packed blocks run -- SGV_KIND_NONE (no packed
+ *   block), _VALU (the packed VALU pass, chunk class form[SGV_PF_VALU_CLASS]),
+ *   _STRIP4 (4-wave 512-column strips), _PAIR (wave-pair strips), _WIDE
+ *   (1,024-column strips on the dense triangles; the other packed blocks, if
+ *   any, behind them as form[SGV_PF_REST_KIND] = _STRIP4 / _PAIR), _STRIP16
+ *   (16x16x4 strips, 9-16 columns), _WALK (band walks);
+ * [SGV_PF_LOAD_FORM]: bytes per lane of the MFMA kernels' matrix loads, 1 = 8 B
+ *   (every f64 matrix), 2 = 16 B; [SGV_PF_FIN_FORM]: the strip finalize, 1 or 4
+ *   threads per panel row (0: none runs); [SGV_PF_PK_WIDTH] / [SGV_PF_PK_PAIRED]:
+ *   the packed right-hand sides' row width in doubles and column order;
+ * [SGV_PF_DENSE]: the dense row-group kernel runs; [SGV_PF_SIDE] /
+ *   [SGV_PF_REST_SIDE]: the set's finalizes overlap its strips on a second
+ *   stream; [SGV_PF_MFMA16]: the pass counts in sgv_timers t[7..9];
+ *   [SGV_PF_IDLE_EXIT]: the wide kernel's idle waves leave at the start. */
+#define SGV_KIND_NONE 0
+#define SGV_KIND_VALU 1
+#define SGV_KIND_STRIP4 2
+#define SGV_KIND_PAIR 3
+#define SGV_KIND_WIDE 4
+#define SGV_KIND_STRIP16 5
+#define SGV_KIND_WALK 6
+#define SGV_PF_KIND 0
+#define SGV_PF_VALU_CLASS 1
+#define SGV_PF_REST_KIND 2
+#define SGV_PF_LOAD_FORM 3
+#define SGV_PF_FIN_FORM 4
+#define SGV_PF_PK_WIDTH 5
+#define SGV_PF_PK_PAIRED 6
+#define SGV_PF_DENSE 7
+#define SGV_PF_SIDE 8
+#define SGV_PF_REST_SIDE 9
+#define SGV_PF_MFMA16 10
+#define SGV_PF_IDLE_EXIT 11
+#define SGV_PF_N 12
+int sgv_ld_pass_form(sgv_ctx* ctx, int ld, int ncol, int32_t* form, int cap);
+
+/* The same decision on the caller's values (host arithmetic, no device, no
+ * context): shape[SGV_PS_N] is what a plan holds -- the packed blocks' element
+ * type (64 / 32), whether it has dense row groups, packed panels, walk tables,
+ * wide strips, 512-column strips beside the wide ones ("rest"), ragged / pair
+ * (0 none, 1 by the launch-tail model, 2 forced) of the 512-column strip set
+ * and of rest, whether the wide kernel's idle waves leave, and the block groups
+ * of the three strip sets; switches[SGV_SW_N] the pass switches as read: -1
+ * unset, else the switch's value (SGV_BAND_WALK 0, SGV_F32_WALK 1, SGV_MF_WIDE
+ * and SGV_MF_PAIR 0 / 1, SGV_MF_WIDE_IDLE 0, SGV_F32_FORM 1 / 2, SGV_FIN_FORM
+ * 1 / 4; anything else is SGV_ERR_ARG). */
+#define SGV_PS_BITS 0
+#define SGV_PS_DENSE 1
+#define SGV_PS_PACKED 2
+#define SGV_PS_WALKS 3
+#define SGV_PS_WIDE 4
+#define SGV_PS_REST 5
+#define SGV_PS_RAGGED 6
+#define SGV_PS_PAIR 7
+#define SGV_PS_REST_RAGGED 8
+#define SGV_PS_REST_PAIR 9
+#define SGV_PS_WIDE_IDLE 10
+#define SGV_PS_NGRP 11
+#define SGV_PS_WIDE_NGRP 12
+#define SGV_PS_REST_NGRP 13
+#define SGV_PS_N 14
+#define SGV_SW_BAND_WALK 0
+#define SGV_SW_F32_WALK 1
+#define SGV_SW_MF_WIDE 2
+#define SGV_SW_MF_PAIR 3
+#define SGV_SW_MF_WIDE_IDLE 4
+#define SGV_SW_F32_FORM 5
+#define SGV_SW_FIN_FORM 6
+#define SGV_SW_N 7
+int sgv_pass_form_model(const int32_t* shape, const int32_t* switches, int mfma_min, int ncol,
+                        int32_t* form, int cap);
 
 /* Synchronise the ctx stream. */
 int sgv_sync(sgv_ctx* ctx);

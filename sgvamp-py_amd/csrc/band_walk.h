@@ -541,10 +541,10 @@ static void launch_walk(const SymWalk* d_walks, int nwalks, const SymPanel* d_pa
                      d_panels, d_items, d_pk, pks, pk_rows, pa, nc, headbuf, carrybuf, partials);
 }
 
-// the walks of float panels (band_walk_f32.hip): the load form by SGV_F32_FORM
+// the walks of float panels (band_walk_f32.hip) in load form `form`
 void launch_walks_f32(int nc, const SymWalk* d_walks, int nwalks, const SymPanel* d_panels,
                       const SymItem* d_items, const double* d_pk, int pks, int64_t pk_rows,
                       const PassArgs& pa, double* headbuf, double* carrybuf, double* partials,
-                      hipStream_t st);
+                      int form, hipStream_t st);
 
 }  // namespace sgv

@@ -30,19 +30,20 @@ __global__ __launch_bounds__(256) void k_walk_fin(const WalkFin* __restrict__ fi
         ((s_w[0 * RW + t] + s_w[1 * RW + t]) + s_w[2 * RW + t]) + s_w[3 * RW + t];
 }
 
-// bits: the stored type of the items' panels (LdPlan::bits)
+// bits: the stored type of the items' panels (LdPlan::bits); form: the float
+// instances' load form; pks: Pk's row width, 4 up to 4 columns and 8 above
 hipError_t launch_band_walk(int nc, const SymWalk* d_walks, int nwalks, const SymPanel* d_panels,
-                            const SymItem* d_items, const double* d_pk, int64_t pk_rows,
+                            const SymItem* d_items, const double* d_pk, int pks, int64_t pk_rows,
                             const PassArgs& pa,
                             double* headbuf, double* carrybuf, const WalkFin* d_fins, int nfins,
-                            double* partials, int bits, hipStream_t st) {
+                            double* partials, int bits, int form, hipStream_t st) {
   if (nc < 1 || nc > 8) return hipErrorInvalidValue;
   if (bits != 64 && bits != 32) return hipErrorInvalidValue;
-  const int pks = nc <= 4 ? 4 : 8;
+  if (pks != (nc <= 4 ? 4 : 8)) return hipErrorInvalidValue;   // the instances' column groups
   if (nwalks > 0) {
     if (bits == 32)
       launch_walks_f32(nc, d_walks, nwalks, d_panels, d_items, d_pk, pks, pk_rows, pa, headbuf,
-                       carrybuf, partials, st);
+                       carrybuf, partials, form, st);
     else if (nc <= 4)
       launch_walk<1, double, 1>(d_walks, nwalks, d_panels, d_items, d_pk, pks, pk_rows, pa, nc,
                                 headbuf, carrybuf, partials, st);

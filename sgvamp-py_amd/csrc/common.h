@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "pass_form.h"
+
 namespace sgv {
 
 constexpr int WAVE = 64;
@@ -384,16 +386,17 @@ int ld_pass_rows_per_group();
 // chunk-width class cls: CW = 1024 >> cls columns per work item
 hipError_t launch_sym_pass(int nc, int cls, const SymItem* d_items, int nitems,
                            const PassArgs& pa, double* rowpart, double* colpart, hipStream_t st);
-// MFMA pass (sym_mfma.hip): launch_pk interleaves the columns into Pk, then
-// launch_sym_mfma runs strips d_strips[0 .. nstrips) (one block group or all)
-// paired: the 5-8-column passes' Pk layout (band walks and strips:
-// strip_pk_paired)
-hipError_t launch_pk(const PassArgs& pa, int nc, int64_t mpad, double* d_pk, hipStream_t st,
-                     bool paired = false);
-bool strip_pk_paired(int nc);
+// MFMA pass (sym_mfma.hip): launch_pk interleaves the columns into Pk (rows of
+// pks doubles; paired: the 5-8-column passes' layout), then launch_sym_mfma runs
+// strips d_strips[0 .. nstrips) (one block group or all).  Which kernel, load
+// form, Pk layout and finalize form a pass takes is pass_form's decision
+// (pass_form.h); the launchers take it as arguments and check only their ranges
+hipError_t launch_pk(const PassArgs& pa, int nc, int64_t mpad, double* d_pk, int pks, bool paired,
+                     hipStream_t st);
 hipError_t launch_sym_mfma(int nc, const SymStrip* d_strips, int nstrips, const SymItem* d_sitems,
-                           const PassArgs& pa, const double* d_pk, double* rowpart,
-                           double* colpart, bool ragged, int pair, int bits, hipStream_t st);
+                           const PassArgs& pa, const double* d_pk, int pks, double* rowpart,
+                           double* colpart, bool ragged, bool pair, int bits, int form,
+                           hipStream_t st);
 // wide strips (3-8 columns, dense-triangle blocks): rowpart per (panel,
 // 1,024-column chunk) item, colpart slots 1,024 wide; idle_exit: waves wholly
 // past a strip's last column leave at once
@@ -404,15 +407,15 @@ hipError_t launch_sym_finalize_wide(int nc, const SymPanelW* d_panels, int npane
                                     const PassArgs& pa, const double* rowpart,
                                     const double* colpart, double* partials, hipStream_t st);
 // band walks (NC <= 8, band_walk.hip): the walks, then the head panels' finalize;
-// bits: the items' stored type (64, or 32: the float instances)
+// bits: the items' stored type (64, or 32: the float instances in load form `form`)
 hipError_t launch_band_walk(int nc, const SymWalk* d_walks, int nwalks, const SymPanel* d_panels,
-                            const SymItem* d_items, const double* d_pk, int64_t pk_rows,
+                            const SymItem* d_items, const double* d_pk, int pks, int64_t pk_rows,
                             const PassArgs& pa, double* headbuf, double* carrybuf,
                             const WalkFin* d_fins, int nfins,
-                            double* partials, int bits, hipStream_t st);
+                            double* partials, int bits, int form, hipStream_t st);
 hipError_t launch_sym_finalize_strip(int nc, const SymPanel* d_panels, int npanels,
                                      const PassArgs& pa, const double* rowpart,
-                                     const double* colpart, double* partials, bool ragged,
+                                     const double* colpart, double* partials, int form,
                                      hipStream_t st);
 hipError_t launch_sym_finalize(int nc, int cls, const SymPanel* d_panels, int npanels,
                                const PassArgs& pa, const double* rowpart, const double* colpart,

@@ -4,7 +4,8 @@
 // units share.  The units: capi.hip (lifetime, staging, vectors, generator,
 // timers), exchange.hip (the ordered cross-rank reductions, RCCL / host
 // exchange, the EM exchange model), ldplan.hip (LD storage, pass plans, the LD
-// pass), solver.hip (CG, LMMSE, denoiser, EM, MLE, the step driver).
+// pass), solver.hip (CG, LMMSE, denoiser, EM, MLE, the step driver).  Which kernel
+// form an LD pass takes is decided in one host-only unit, pass_form.cpp.
 #pragma once
 #include "common.h"
 #include "hybrd.h"
@@ -92,7 +93,7 @@ struct StripSet {
 struct LdPlan {
   bool valid = false;
   int bits = 64;               // element type of every packed block (one per LD matrix: the
-                               // strip tables are single-typed); 32: every pass on s512
+                               // strip tables are single-typed); 32: pass_form keeps it on s512
   RowGroup* d_rg = nullptr;    // dense blocks
   int nrg = 0;
   int* d_pbeg = nullptr;       // partial slots of block b: [pbeg[b], pbeg[b+1])
@@ -108,7 +109,7 @@ struct LdPlan {
   // blocks, and the 512-column strips of the plan's other packed blocks (band
   // blocks; empty when there are none): a pass that takes the wide form runs
   // `wide`, then `rest` with its partials behind the wide ones.  Which form a
-  // block takes depends on the block and the pass's column count alone.
+  // pass takes is pass_form's decision (pass_form.h) over the plan's shape.
   StripSet wide, rest;
   bool wide_idle = true;       // k_sym_mfma_wide: idle waves leave at the start
   // band walks (band_walk.hip, 3-8 columns): when every packed block is a band
@@ -136,8 +137,6 @@ struct LdPlan {
   double cpl_bytes = 0.0;      // coupling matrix bytes read per pass (this rank)
 };
 
-// chunk-width class of the packed VALU pass for nc columns (CW = 1024 >> cls)
-static inline int sym_class(int nc) { return nc <= 2 ? 0 : nc <= 4 ? 1 : nc <= 8 ? 2 : 3; }
 // default number of right-hand sides from which packed passes run on the f64
 // matrix cores (sym_mfma.hip, class-1 items); per context: sgv_set_mfma_min
 // (0 disables)

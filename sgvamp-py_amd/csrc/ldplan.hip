@@ -167,11 +167,10 @@ static double lpt_efficiency(std::vector<double> cost, int slots) {
 // passes when its launch drains with at least 3 % less tail by the strips'
 // model cost (a few strips per slot: an 8-block share of the north star, 0.924
 // against 0.986 of a perfect split; 16 blocks and 8 x 25,000 stay on the 4-wave
-// kernel); SGV_MF_PAIR=0 / 1 (with SGV_AB=1) forces none / every pass (2).
+// kernel); forced (plan_pair_forced: SGV_MF_PAIR): none (0) / every pass (2).
 static int mfma_pair_choice(const std::vector<SymStrip>& strips,
-                            const std::vector<SymItem>& sitems) {
-  const char* e = ab_env("SGV_MF_PAIR");
-  if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1' ? 2 : 0;
+                            const std::vector<SymItem>& sitems, int forced) {
+  if (forced >= 0) return forced;
   const int ncu = device_cus();
   std::vector<double> cost;
   cost.reserve(strips.size());
@@ -200,7 +199,7 @@ static int mfma_pair_choice(const std::vector<SymStrip>& strips,
 // the taken blocks' panels only; a strip's shape depends on its block alone.
 static int build_strips(sgv_ctx* c, int ld, const std::vector<SymItem>& items,
                         const std::vector<SymPanel>& panels, bool wide, int which,
-                        StripSet* out) {
+                        int pair_forced, StripSet* out) {
   const int cw = wide ? MFW_CW : 512;
   const int S = MFMA_STRIP;
   const int NPAR = cw / SYM_H;       // chunks start at 256 p + cw k
@@ -342,7 +341,7 @@ static int build_strips(sgv_ctx* c, int ld, const std::vector<SymItem>& items,
   out->ragged = false;
   for (const SymStrip& st : strips)
     for (int i = 0; i < st.npan; ++i) out->ragged |= sitems[st.it0 + i].nc < st.ncmax;
-  out->pair = (wide || out->ragged) ? 0 : mfma_pair_choice(strips, sitems);
+  out->pair = (wide || out->ragged) ? 0 : mfma_pair_choice(strips, sitems, pair_forced);
   CHK(upload_table(c, strips, &out->d_strips));
   CHK(upload_table(c, sitems, &out->d_sitems));
   if (wide) {
@@ -361,20 +360,24 @@ static int build_strips(sgv_ctx* c, int ld, const std::vector<SymItem>& items,
   return SGV_OK;
 }
 
-// Which passes take the wide strips on dense-triangle blocks: every 3-8-column
-// pass (one box, parent and this build alternating three times,
-// profiles/r07/ldpass_ab.jsonl: 64 x 15,625 at 4 columns -2.1 % per pass, the
-// 8-block share -1.5 %; the north star's bench line +2.3 % it/s).
-// SGV_MF_WIDE=0 / 1 (with SGV_AB=1): none / every 3-8-column pass; a forced
-// SGV_MF_PAIR keeps the 512-column forms it selects between.  A function of
-// the column count alone, read per pass (a getenv).
-static bool wide_pass(int nc) {
-  if (nc < 3 || nc > 8) return false;
-  const char* e = ab_env("SGV_MF_WIDE");
-  if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
-  const char* p = ab_env("SGV_MF_PAIR");
-  if (p && (p[0] == '0' || p[0] == '1')) return false;
-  return true;
+// The seven pass switches, read here and nowhere else: when a plan is built
+// (ensure_plan: what the plan keeps) and at each pass (ld_pass, sgv_ld_pass_form)
+// -- never cached, tests change them during an engine's life.  A value that is
+// not one of the switch's own counts as unset.
+static PassSwitches read_pass_switches() {
+  auto sw = [](const char* name, char a, char b) {
+    const char* e = ab_env(name);
+    return e && (e[0] == a || e[0] == b) ? e[0] - '0' : -1;
+  };
+  PassSwitches s;
+  s.band_walk = sw("SGV_BAND_WALK", '0', '0');
+  s.f32_walk = sw("SGV_F32_WALK", '1', '1');
+  s.mf_wide = sw("SGV_MF_WIDE", '0', '1');
+  s.mf_pair = sw("SGV_MF_PAIR", '0', '1');
+  s.mf_wide_idle = sw("SGV_MF_WIDE_IDLE", '0', '0');
+  s.f32_form = sw("SGV_F32_FORM", '1', '2');
+  s.fin_form = sw("SGV_FIN_FORM", '1', '4');
+  return s;
 }
 
 // Band walks of LD matrix ld (band_walk.hip) from the class-1 tables in
@@ -385,35 +388,10 @@ static bool wide_pass(int nc) {
 // column part inside the walk or the one before it.  A walk that does not start
 // its block has min(R - 1, np) head panels; one that does not end it leaves
 // min(R - 1, panels after it) carry slots.
-// The walks run the band passes of up to 8 columns (two 4x4x4 column groups;
-// 9-16 columns stay on the strips' 16x16x4 kernel): at M = 1e6, bw = 1,000
-// 1.68 / 1.71 / 1.99 ms at 3 / 4 / 8 columns against the strips' 1.87 / 1.92
-// / 2.12 (profiles/r05/walk_ab/wvs_a_ab.jsonl).
-// SGV_BAND_WALK=0 (with SGV_AB=1): the strips for every band pass (the
-// walks-vs-strips A/B of tools/gpu_walk_vs_strips.sh).
-// An f32 band matrix (sgv_set_ld_precision 32) stays on the 512-column strips at
-// every column count: the walks' float instances measured 1.27-1.33x the strips'
-// time at 3-4 columns and 1.26-1.31x at 5-8 (M = 1e6, bw = 1,000 and 500, one
-// box, alternating: profiles/ld_f32_walk/ldpass_band_ab.jsonl) --
-// with half the bytes the walk is bound by its one workgroup's tile, chain and
-// hand-off work per sub-tile, which the strips spread over two workgroups per CU.
-// SGV_F32_WALK=1 (with SGV_AB=1): an f32 band-only matrix takes the walks at 3-8
-// columns, whatever sgv_set_mfma_min says (1-2 and 9-16 columns stay on the
-// strips) -- the arm of that A/B, and how the tests reach the float instances.
-// Read when the plan is built (the walk tables) and per pass (a getenv).
-constexpr int WALK_F32_MIN_NC = 3;
-static bool f32_walk_on() {
-  const char* e = ab_env("SGV_F32_WALK");
-  return e && e[0] == '1';
-}
-static int band_walk_max_nc() {
-  const char* e = ab_env("SGV_BAND_WALK");
-  return (e && e[0] == '0') ? 0 : 8;
-}
-
+// Which passes walk, and under which switches a plan gets walk tables at all:
+// pass_form.cpp.
 static int plan_walks(sgv_ctx* c, int ld, const std::vector<SymItem>& items,
                       const std::vector<SymPanel>& panels, LdPlan* pl) {
-  if (band_walk_max_nc() == 0) return SGV_OK;
   bool any = false;
   for (int b = 0; b < c->nblk; ++b) {
     const LdBlock& lb = c->ldb[ld][b];
@@ -615,7 +593,9 @@ int ensure_plan(sgv_ctx* c, int ld){
     }
     pl.bits = first >= 0 ? c->ldb[ld][first].bits : 64;
   }
-  const bool f32 = pl.bits == 32;   // every pass on the 512-column strips (ld_pass; A/B: walks)
+  const bool f32 = pl.bits == 32;   // every pass on the 512-column strips (pass_form; A/B: walks)
+  const PassSwitches sw = read_pass_switches();
+  const int pair_forced = plan_pair_forced(sw);
   std::vector<RowGroup> rg;
   std::vector<int> pbeg(c->nblk + 1, 0);
   const int rows = ld_pass_rows_per_group();
@@ -704,16 +684,13 @@ int ensure_plan(sgv_ctx* c, int ld){
     }
     CHK(upload_table(c, panels, &pl.d_panels[cls]));
     if (cls == 0 && !f32) {
-      CHK(build_strips(c, ld, items, panels, true, 1, &pl.wide));
-      // SGV_MF_WIDE_IDLE=0 (with SGV_AB=1): the idle waves of a ragged chunk stay
-      // and add zeros (the A/B of their exit)
-      const char* e = ab_env("SGV_MF_WIDE_IDLE");
-      pl.wide_idle = !(e && e[0] == '0');
+      CHK(build_strips(c, ld, items, panels, true, 1, pair_forced, &pl.wide));
+      pl.wide_idle = plan_wide_idle(sw);
     }
     if (cls == 1) {
-      CHK(build_strips(c, ld, items, panels, false, 0, &pl.s512));
-      if (pl.wide.nstrips) CHK(build_strips(c, ld, items, panels, false, 2, &pl.rest));
-      if (!f32 || f32_walk_on()) CHK(plan_walks(c, ld, items, panels, &pl));
+      CHK(build_strips(c, ld, items, panels, false, 0, pair_forced, &pl.s512));
+      if (pl.wide.nstrips) CHK(build_strips(c, ld, items, panels, false, 2, pair_forced, &pl.rest));
+      if (plan_wants_walks(pl.bits, sw)) CHK(plan_walks(c, ld, items, panels, &pl));
     }
     const size_t ncmax = (size_t)sym_class_nc(cls);
     rowpart_need = std::max(rowpart_need, items.size() * SYM_H * ncmax);
@@ -758,10 +735,31 @@ static int coupling_pass(sgv_ctx* c, const LdPlan& pl, int nc, const PassArgs& p
   return SGV_OK;
 }
 
+// what pass_form needs from a plan
+static PlanShape plan_shape(const LdPlan& pl) {
+  PlanShape ps;
+  ps.bits = pl.bits;
+  ps.dense = pl.nrg > 0;
+  ps.packed = pl.npanels > 0;
+  ps.walks = pl.nwalks > 0;
+  ps.wide = pl.wide.nstrips > 0;
+  ps.rest = pl.rest.nstrips > 0;
+  ps.ragged = pl.s512.ragged;
+  ps.pair = pl.s512.pair;
+  ps.rest_ragged = pl.rest.ragged;
+  ps.rest_pair = pl.rest.pair;
+  ps.wide_idle = pl.wide_idle;
+  ps.ngrp = pl.s512.ngrp;
+  ps.wide_ngrp = pl.wide.ngrp;
+  ps.rest_ngrp = pl.rest.ngrp;
+  return ps;
+}
+
 int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
   if (nc <= 0) return SGV_OK;
   CHK(ensure_plan(c, ld));
   const LdPlan& pl = c->plan[ld];
+  const PassForm f = pass_form(plan_shape(pl), nc, c->mfma_min, read_pass_switches());
   PassArgs pa = pa_in;
   pa.cpbuf = c->d_cpbuf;
   hipEvent_t e0, e1;
@@ -776,100 +774,83 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
   }
   HIPCHK(hipEventRecord(e0, c->st));
   if (pl.halo || pl.nctasks) CHK(coupling_pass(c, pl, nc, pa));
-  if (pl.nrg) HIPCHK(launch_ld_pass(nc, c->d_blks[ld], pl.d_rg, pl.nrg, pa, c->d_part, c->st));
-  if (pl.npanels) {
-    // an f32 matrix: every column count on the 512-column strips, whatever
-    // mfma_min says (its plan holds no wide strips, and walks only for the
-    // SGV_F32_WALK A/B: then a band plan's 3-8-column passes take them)
-    const bool f32 = pl.bits == 32;
-    const bool mf = f32 || (c->mfma_min > 0 && nc >= c->mfma_min);
-    const int cls = mf ? 1 : sym_class(nc);
-    if (mf) {
-      const bool walk = pl.nwalks && nc <= band_walk_max_nc() &&
-                        (!f32 || (nc >= WALK_F32_MIN_NC && f32_walk_on()));
-      double mf_aux = 0.0;
-      HIPCHK(launch_pk(pa, nc, c->Mpad, c->d_pk, c->st,
-                       walk ? nc > 4 : strip_pk_paired(nc)));
-      if (walk) {   // band plan: the walks, then the head panels
-        HIPCHK(launch_band_walk(nc, pl.d_walks, pl.nwalks, pl.d_wpanels, pl.d_witems, c->d_pk,
-                                c->Mpad, pa,
-                                c->d_whead, c->d_wcarry, pl.d_wfins, pl.nwfins, c->d_part, pl.bits,
-                                c->st));
-      } else {
-        // One strip set: group g's strips on the ctx stream, its finalize on the
-        // side stream behind them, so the finalize (and the launch tail) of g
-        // overlaps g + 1's strips.  Same work items, so the products are bitwise
-        // the one-launch pass's; the pass's events (e0 on st, e1 after the join)
-        // span both.  rp / cp: the set's partials
-        const bool usew = !f32 && pl.wide.nstrips > 0 && wide_pass(nc);
-        bool side = false;
-        auto run_set = [&](const StripSet& ss, bool wide, double* rp, double* cp) -> int {
-          for (int g = 0; g < ss.ngrp; ++g) {
-            const int s0 = ss.gs[g], ns = ss.gs[g + 1] - s0;
-            const int p0 = ss.gp[g], npn = ss.gp[g + 1] - p0;
-            const bool split = ss.ngrp > 1;
-            if (wide)
-              HIPCHK(launch_sym_mfma_wide(nc, ss.d_strips + s0, ns, ss.d_sitems, pa, c->d_pk, rp,
-                                          cp, pl.wide_idle, c->st));
-            else
-              HIPCHK(launch_sym_mfma(nc, ss.d_strips + s0, ns, ss.d_sitems, pa, c->d_pk, rp, cp,
-                                     ss.ragged, f32 ? 0 : ss.pair, pl.bits, c->st));
-            hipStream_t fs = c->st;
-            if (split) {
-              HIPCHK(hipEventRecord(c->ev_grp[g % MAXGRP], c->st));
-              HIPCHK(hipStreamWaitEvent(c->st_fin, c->ev_grp[g % MAXGRP], 0));
-              fs = c->st_fin;
-              side = true;
-            }
-            if (wide)
-              HIPCHK(launch_sym_finalize_wide(nc, ss.d_wpanels + p0, npn, pa, rp, cp, c->d_part,
-                                              fs));
-            else
-              HIPCHK(launch_sym_finalize_strip(nc, ss.d_panels + p0, npn, pa, rp, cp, c->d_part,
-                                               ss.ragged, fs));
-          }
-          return SGV_OK;
-        };
-        if (usew) {
-          CHK(run_set(pl.wide, true, c->d_rowpart, c->d_colpart));
-          if (pl.rest.nstrips)
-            CHK(run_set(pl.rest, false, c->d_rowpart + (size_t)pl.wide.nslots_items * SYM_H * nc,
-                        c->d_colpart + (size_t)pl.wide.nstrips * MFW_CW * nc));
-          mf_aux = 2.0 * 8.0 * nc * ((double)pl.wide.nsitems * SYM_H +
-                                     (double)pl.wide.nstrips * MFW_CW +
-                                     (double)pl.rest.nsitems * SYM_H +
-                                     (double)pl.rest.nstrips * 512);
-        } else {
-          CHK(run_set(pl.s512, false, c->d_rowpart, c->d_colpart));
-          mf_aux = 2.0 * 8.0 * nc * ((double)pl.s512.nsitems * SYM_H +
-                                     (double)pl.s512.nstrips * 512);
-        }
-        if (side) {
-          HIPCHK(hipEventRecord(c->ev_fin, c->st_fin));
-          HIPCHK(hipStreamWaitEvent(c->st, c->ev_fin, 0));
-        }
-      }
-      if (walk)   // head partials and carries, written and read
-        c->aux_bytes += 2.0 * 8.0 * nc * SYM_H * (double)(pl.nhslots + pl.ncslots);
-      else   // the row and column partials of the strips launched, written and read
-        c->aux_bytes += mf_aux;
-      c->aux_bytes += 8.0 * (double)c->Mpad * ((nc <= 4 ? 4 : nc <= 8 ? 8 : 16) + nc);   // Pk pack
+  if (f.dense) HIPCHK(launch_ld_pass(nc, c->d_blks[ld], pl.d_rg, pl.nrg, pa, c->d_part, c->st));
+  if (f.kind == PK_VALU) {
+    const int cls = f.valu_class;
+    HIPCHK(launch_sym_pass(nc, cls, pl.d_items[cls], pl.nitems[cls], pa, c->d_rowpart,
+                           c->d_colpart, c->st));
+    HIPCHK(launch_sym_finalize(nc, cls, pl.d_panels[cls], pl.npanels, pa, c->d_rowpart,
+                               c->d_colpart, c->d_part, c->st));
+    const double cw = (double)(1024 >> cls);
+    c->aux_bytes += 2.0 * 8.0 * nc * (double)pl.nitems[cls] * (SYM_H + cw);
+  } else if (f.kind != PK_NONE) {
+    HIPCHK(launch_pk(pa, nc, c->Mpad, c->d_pk, f.pk_width, f.pk_paired, c->st));
+    if (f.kind == PK_WALK) {   // band plan: the walks, then the head panels
+      HIPCHK(launch_band_walk(nc, pl.d_walks, pl.nwalks, pl.d_wpanels, pl.d_witems, c->d_pk,
+                              f.pk_width, c->Mpad, pa, c->d_whead, c->d_wcarry, pl.d_wfins,
+                              pl.nwfins, c->d_part, pl.bits, f.load_form, c->st));
+      // head partials and carries, written and read
+      c->aux_bytes += 2.0 * 8.0 * nc * SYM_H * (double)(pl.nhslots + pl.ncslots);
     } else {
-      HIPCHK(launch_sym_pass(nc, cls, pl.d_items[cls], pl.nitems[cls], pa, c->d_rowpart,
-                             c->d_colpart, c->st));
-      HIPCHK(launch_sym_finalize(nc, cls, pl.d_panels[cls], pl.npanels, pa, c->d_rowpart,
-                                 c->d_colpart, c->d_part, c->st));
-      const double cw = (double)(1024 >> cls);
-      c->aux_bytes += 2.0 * 8.0 * nc * (double)pl.nitems[cls] * (SYM_H + cw);
+      // One strip set: group g's strips on the ctx stream, its finalize on the
+      // side stream behind them, so the finalize (and the launch tail) of g
+      // overlaps g + 1's strips.  Same work items, so the products are bitwise
+      // the one-launch pass's; the pass's events (e0 on st, e1 after the join)
+      // span both.  rp / cp: the set's partials
+      auto run_set = [&](const StripSet& ss, int kind, bool split, double* rp, double* cp) -> int {
+        for (int g = 0; g < ss.ngrp; ++g) {
+          const int s0 = ss.gs[g], ns = ss.gs[g + 1] - s0;
+          const int p0 = ss.gp[g], npn = ss.gp[g + 1] - p0;
+          if (kind == PK_WIDE)
+            HIPCHK(launch_sym_mfma_wide(nc, ss.d_strips + s0, ns, ss.d_sitems, pa, c->d_pk, rp,
+                                        cp, f.idle_exit, c->st));
+          else
+            HIPCHK(launch_sym_mfma(nc, ss.d_strips + s0, ns, ss.d_sitems, pa, c->d_pk,
+                                   f.pk_width, rp, cp, ss.ragged, kind == PK_PAIR, pl.bits,
+                                   f.load_form, c->st));
+          hipStream_t fs = c->st;
+          if (split) {
+            HIPCHK(hipEventRecord(c->ev_grp[g % MAXGRP], c->st));
+            HIPCHK(hipStreamWaitEvent(c->st_fin, c->ev_grp[g % MAXGRP], 0));
+            fs = c->st_fin;
+          }
+          if (kind == PK_WIDE)
+            HIPCHK(launch_sym_finalize_wide(nc, ss.d_wpanels + p0, npn, pa, rp, cp, c->d_part,
+                                            fs));
+          else
+            HIPCHK(launch_sym_finalize_strip(nc, ss.d_panels + p0, npn, pa, rp, cp, c->d_part,
+                                             f.fin_form, fs));
+        }
+        return SGV_OK;
+      };
+      // the row and column partials of the strips launched, written and read
+      if (f.kind == PK_WIDE) {
+        CHK(run_set(pl.wide, PK_WIDE, f.side, c->d_rowpart, c->d_colpart));
+        if (f.rest_kind != PK_NONE)
+          CHK(run_set(pl.rest, f.rest_kind, f.rest_side,
+                      c->d_rowpart + (size_t)pl.wide.nslots_items * SYM_H * nc,
+                      c->d_colpart + (size_t)pl.wide.nstrips * MFW_CW * nc));
+        c->aux_bytes += 2.0 * 8.0 * nc * ((double)pl.wide.nsitems * SYM_H +
+                                          (double)pl.wide.nstrips * MFW_CW +
+                                          (double)pl.rest.nsitems * SYM_H +
+                                          (double)pl.rest.nstrips * 512);
+      } else {
+        CHK(run_set(pl.s512, f.kind, f.side, c->d_rowpart, c->d_colpart));
+        c->aux_bytes += 2.0 * 8.0 * nc * ((double)pl.s512.nsitems * SYM_H +
+                                          (double)pl.s512.nstrips * 512);
+      }
+      if (f.side || f.rest_side) {
+        HIPCHK(hipEventRecord(c->ev_fin, c->st_fin));
+        HIPCHK(hipStreamWaitEvent(c->st, c->ev_fin, 0));
+      }
     }
+    c->aux_bytes += 8.0 * (double)c->Mpad * (f.pk_width + nc);   // Pk pack
   }
   HIPCHK(hipEventRecord(e1, c->st));
   c->pending.emplace_back(e0, e1);
-  const bool wide = nc > 8 && pl.npanels &&
-                    (pl.bits == 32 || (c->mfma_min > 0 && nc >= c->mfma_min));
-  c->pending_wide.push_back(wide ? 1 : 0);
+  c->pending_wide.push_back(f.mfma16 ? 1 : 0);
   c->ld_flops += 2.0 * nc * pl.mac_elems;
-  if (wide) {
+  if (f.mfma16) {
     c->ld_flops_wide += 2.0 * nc * pl.mac_elems;
     c->ld_launches_wide += 1.0;
   }
@@ -877,6 +858,16 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
   c->ld_bytes += pl.stored_bytes;
   c->dense_bytes += pl.dense_bytes;
   c->rhs_bytes += 2.0 * nc * (double)c->Mloc * 8.0;
+  return SGV_OK;
+}
+
+extern "C" int sgv_ld_pass_form(sgv_ctx* c, int ld, int ncol, int32_t* form, int cap) {
+  ENTER(c);
+  if (ld < 0 || ld >= c->nld || ncol < 1 || ncol > MAXC || !form || cap < 0)
+    return fail(c, SGV_ERR_ARG, "sgv_ld_pass_form: bad arguments");
+  CHK(ensure_plan(c, ld));
+  pass_form_ints(pass_form(plan_shape(c->plan[ld]), ncol, c->mfma_min, read_pass_switches()),
+                 form, cap);
   return SGV_OK;
 }
 

@@ -65,11 +65,6 @@ __device__ unsigned long long g_mf_trace[3 * MF_TRACE_MAX];
 #define MF_TRACE_END
 #endif
 
-// the form an f32 matrix runs: 2, faster than 1 on every line of the A/B (64 x
-// 15,625 -1...-5 % per pass, 8 x 15,625 -3...-9 %: DESIGN.md 4.6,
-// profiles/ld_f32/ldpass_ab.jsonl); 1 stays compiled as the bitwise pin
-constexpr int F32_FORM_DEFAULT = 2;
-
 constexpr int MF_CW = 512;   // chunk width (class 1 items)
 constexpr int MF_LDP = 34;   // k_sym_mfma16's staging row pitch (doubles): conflict-free both ways
 
@@ -830,22 +825,11 @@ __global__ __launch_bounds__(256) void k_pack(PassArgs pa, int ncol, int64_t mpa
 
 // ragged: some strip item stops short of its strip's widest (band blocks):
 // the RAG kernels, without the deferred row MFMAs (even there,
-// profiles/r04/band2_ab.jsonl).  pair: the plan's choice of the wave-pair
-// kernel (ldplan.hip mfma_pair_choice; bitwise the same products) -- 1: by the
-// launch-tail model (a short launch: the 8-block share of the north star), 2
-// (forced, SGV_MF_PAIR=1): every launch.  Since the column operands are loaded
-// once per row group the model's choice holds at 5-8 columns too: the 8-block
-// share -2...-8 %, 4 x 25,000 -2.6 % per 8-column pass; launches it does not
-// pick run +1.4...+9 % with the pair form (profiles/r06/pair58_*.jsonl)
+// profiles/r04/band2_ab.jsonl).  pair: the wave-pair kernel.
 // f32 (the tables' panels hold floats): the float instances of the same two
-// 4-wave kernels -- RAG for band plans, DEF otherwise; there is no float pair form
-// SGV_F32_FORM (A/B, with SGV_AB=1): the float kernels' load form -- 1 = 8 B per
-// lane (bitwise the f64 strips on the widened matrix), 2 = 16 B per lane
-// (frag_col); read per launch (a getenv)
-static int f32_form() {
-  const char* e = ab_env("SGV_F32_FORM");
-  return (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : F32_FORM_DEFAULT;
-}
+// 4-wave kernels -- RAG for band plans, DEF otherwise; there is no float pair form.
+// form: the float kernels' load form.  pair, form, pks and the finalize's form
+// are pass_form's (pass_form.cpp, with what was measured).
 
 // The (stored type, load form, ragged) instance of a 4-wave strip kernel a
 // launch takes, chosen once: f(StripInst<T, LF, RAG>{}) launches it.
@@ -856,9 +840,8 @@ struct StripInst {
   static constexpr bool rag = RAG;
 };
 template <class F>
-static void with_strip_inst(bool f32, bool ragged, F f) {
-  const int form = f32 ? f32_form() : 1;
-  if (form == 2)
+static void with_strip_inst(bool f32, bool ragged, int form, F f) {
+  if (f32 && form == 2)
     ragged ? f(StripInst<float, 2, true>{}) : f(StripInst<float, 2, false>{});
   else if (f32)
     ragged ? f(StripInst<float, 1, true>{}) : f(StripInst<float, 1, false>{});
@@ -869,13 +852,14 @@ static void with_strip_inst(bool f32, bool ragged, F f) {
 template <int NG, bool PP = false>
 static void launch_mf(const SymStrip* d_strips, int nstrips, const SymItem* d_sitems,
                       const double* d_pk, int nc, double* rowpart, double* colpart,
-                      const int* run, int pks, bool ragged, int pair, bool f32, hipStream_t st) {
+                      const int* run, int pks, bool ragged, bool pair, bool f32, int form,
+                      hipStream_t st) {
   // prefetch depth 2 measured best (PD 1/2/4: 11.64/11.16/12.27 ms at NC=4, M=1e6)
-  if (!f32 && !ragged && pair >= 1)
+  if (pair)
     hipLaunchKernelGGL((k_sym_mfma_pair<NG, 2, PP>), dim3(nstrips), dim3(512), 0, st, d_strips,
                        d_sitems, d_pk, nc, rowpart, colpart, run, pks);
   else
-    with_strip_inst(f32, ragged, [&](auto i) {
+    with_strip_inst(f32, ragged, form, [&](auto i) {
       typedef decltype(i) I;   // RAG for band plans, DEF otherwise
       hipLaunchKernelGGL((k_sym_mfma<NG, 2, I::rag, !I::rag, PP, typename I::elem, I::lf>),
                          dim3(nstrips), dim3(256), 0, st, d_strips, d_sitems, d_pk, nc, rowpart,
@@ -883,16 +867,10 @@ static void launch_mf(const SymStrip* d_strips, int nstrips, const SymItem* d_si
     });
 }
 
-// 5-8-column strip passes read Pk PAIRED (k_pack), in either strip kernel.
-// Bitwise the same products; one box,
-// alternating: the 8-block share -0.6...-1.8 % per pass, 64 blocks even to
-// -0.4 % (profiles/r06/pkpair_ab.jsonl, pkpair_bench.jsonl)
-bool strip_pk_paired(int nc) { return nc > 4 && nc <= 8; }
-
-hipError_t launch_pk(const PassArgs& pa, int nc, int64_t mpad, double* d_pk, hipStream_t st,
-                     bool paired) {
+hipError_t launch_pk(const PassArgs& pa, int nc, int64_t mpad, double* d_pk, int pks, bool paired,
+                     hipStream_t st) {
   if (nc < 1 || nc > 16) return hipErrorInvalidValue;
-  const int pks = nc > 8 ? 16 : nc <= 4 ? 4 : 8;
+  if ((pks != 4 && pks != 8 && pks != 16) || nc > pks) return hipErrorInvalidValue;
   const dim3 pg((unsigned)((mpad + 255) / 256));
   if (pks == 4)
     hipLaunchKernelGGL(k_pack<4>, pg, dim3(256), 0, st, pa, nc, mpad, d_pk);
@@ -906,14 +884,15 @@ hipError_t launch_pk(const PassArgs& pa, int nc, int64_t mpad, double* d_pk, hip
 }
 
 hipError_t launch_sym_mfma(int nc, const SymStrip* d_strips, int nstrips, const SymItem* d_sitems,
-                           const PassArgs& pa, const double* d_pk, double* rowpart,
-                           double* colpart, bool ragged, int pair, int bits, hipStream_t st) {
+                           const PassArgs& pa, const double* d_pk, int pks, double* rowpart,
+                           double* colpart, bool ragged, bool pair, int bits, int form,
+                           hipStream_t st) {
   if (nc < 1 || nc > 16) return hipErrorInvalidValue;
   if (bits != 64 && bits != 32) return hipErrorInvalidValue;
   const bool f32 = bits == 32;
   if (f32 && pair) return hipErrorInvalidValue;   // no float instance of the pair form
+  if (pair && (ragged || nc > 8)) return hipErrorInvalidValue;   // nor a ragged or 16-column one
   if (nstrips <= 0) return hipSuccess;
-  const int pks = nc > 8 ? 16 : nc <= 4 ? 4 : 8;
   // 9..16 columns: one 16x16x4 group beats three/four 4x4x4 groups (register
   // pressure) and two 8-column wave sets of the 4x4x4 kernel in one 8-wave
   // workgroup re-reading the same R with the default cache policy (+33 %,
@@ -930,17 +909,20 @@ hipError_t launch_sym_mfma(int nc, const SymStrip* d_strips, int nstrips, const 
   // issues cost more than they save; the spill-free form kept is the row
   // operands of the last step(s) in LDS (below).
   switch ((nc + 3) / 4) {
-    case 1: launch_mf<1>(d_strips, nstrips, d_sitems, d_pk, nc, rowpart, colpart, pa.run, pks, ragged, pair, f32, st); break;
-    case 2:   // Pk paired (strip_pk_paired)
+    case 1:
+      launch_mf<1>(d_strips, nstrips, d_sitems, d_pk, nc, rowpart, colpart, pa.run, pks, ragged,
+                   pair, f32, form, st);
+      break;
+    case 2:   // Pk paired
       launch_mf<2, true>(d_strips, nstrips, d_sitems, d_pk, nc, rowpart, colpart, pa.run, pks,
-                         ragged, pair, f32, st);
+                         ragged, pair, f32, form, st);
       break;
     default:
       // the row operands of the last steps in LDS, so nothing spills (256 VGPRs
       // with 3 / 7 spilled before): band plans the last 2 steps (-0.6 % per
       // 16-column band pass), dense plans the last one (even; 2 steps there +2 %)
       // -- profiles/r06/mf16_bl_*.jsonl, mf16_tb_*.jsonl; products bitwise equal
-      with_strip_inst(f32, ragged, [&](auto i) {
+      with_strip_inst(f32, ragged, form, [&](auto i) {
         typedef decltype(i) I;
         hipLaunchKernelGGL((k_sym_mfma16<2, I::rag, I::rag ? 2 : 1, typename I::elem, I::lf>),
                            dim3(nstrips), dim3(256), 0, st, d_strips, d_sitems, d_pk, nc, rowpart,
@@ -959,7 +941,7 @@ hipError_t launch_sym_mfma_wide(int nc, const SymStrip* d_strips, int nstrips,
   if (nc <= 4)
     hipLaunchKernelGGL((k_sym_mfma_wide<1, 2>), dim3(nstrips), dim3(512), 0, st, d_strips,
                        d_sitems, d_pk, nc, rowpart, colpart, pa.run, idle_exit ? 1 : 0);
-  else   // Pk paired (strip_pk_paired)
+  else   // Pk paired
     hipLaunchKernelGGL((k_sym_mfma_wide<2, 2, true>), dim3(nstrips), dim3(512), 0, st, d_strips,
                        d_sitems, d_pk, nc, rowpart, colpart, pa.run, idle_exit ? 1 : 0);
   return hipGetLastError();
@@ -990,26 +972,18 @@ extern "C" int sgv_diag_mf_trace(unsigned long long* out, int n) {
 }
 #endif
 
-// SGV_FIN_FORM (A/B, with SGV_AB=1): the strip finalize's form -- 4 = FIN_Q
-// threads per panel row (k_sym_finalize_strip), 1 = one thread per row with the
-// parts in registers (k_sym_finalize_strip1; bitwise the same outputs);
-// default: 1 for band plans at up to 8 columns (M = 1e6, bw = 1,000: 2.126-2.134
-// vs 2.156 ms per pass), 4 otherwise (dense 64 x 15,625 at 8 columns: 12.13 vs
-// 11.97-12.01 ms; 16 columns even; profiles/r04/fin_*.jsonl)
-static int fin_form(bool ragged, int nc) {
-  const char* e = ab_env("SGV_FIN_FORM");   // per launch (a getenv): tests switch it
-  const int v = (e && (e[0] == '1' || e[0] == '4')) ? e[0] - '0' : 0;
-  return v ? v : (ragged && nc <= 8) ? 1 : 4;
-}
-
+// form: 4 = FIN_Q threads per panel row (k_sym_finalize_strip), 1 = one thread
+// per row with the parts in registers (k_sym_finalize_strip1; bitwise the same
+// outputs)
 hipError_t launch_sym_finalize_strip(int nc, const SymPanel* d_panels, int npanels,
                                      const PassArgs& pa, const double* rowpart,
-                                     const double* colpart, double* partials, bool ragged,
+                                     const double* colpart, double* partials, int form,
                                      hipStream_t st) {
   // the partials with the default cache policy: nontemporal loads measured
   // 0.5-3 % slower (profiles/r03/s4/fin_nt_ab.jsonl; they were just written)
   if (npanels <= 0) return hipSuccess;   // a block group without packed panels
-  const bool one = fin_form(ragged, nc) == 1;
+  if (form != 1 && form != 4) return hipErrorInvalidValue;
+  const bool one = form == 1;
 #define FIN_CASE(N)                                                                        \
   case N:                                                                                  \
     if (one)                                                                               \

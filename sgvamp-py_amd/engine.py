@@ -564,6 +564,15 @@ class Engine:
         self.ctx.sgv_ld_block_precision(int(ld), b_global - self.b0, hb.iptr(f))
         return int(f[0])
 
+    def ld_pass_form(self, ld, ncol):
+        """The kernel form the next pass of ncol columns over LD matrix ld takes
+        (hb.PassForm: the packed kind by name, load and finalize forms, Pk layout,
+        ...), under the switches as that pass would read them.  Host only, beyond
+        the plan tables a first pass builds anyway."""
+        f = np.zeros(len(hb.PASS_FORM_FIELDS), dtype=np.int32)
+        self.ctx.sgv_ld_pass_form(int(ld), int(ncol), hb.iptr(f), len(f))
+        return hb.pass_form_of(f)
+
     def ld_block_format(self, ld, b_global):
         f = np.zeros(1, dtype=np.int32)
         self.ctx.sgv_ld_block_format(int(ld), b_global - self.b0, hb.iptr(f))

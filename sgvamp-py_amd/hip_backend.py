@@ -4,6 +4,7 @@ There is no CPU fallback: if the library or a HIP device is missing, every entry
 point raises.  Build the library with ``make -C sgvamp-py_amd/csrc`` (or
 ``python -c "import __graft_entry__ as g; g.build()"``).
 """
+import collections
 import ctypes
 import os
 
@@ -26,6 +27,17 @@ MAX_COHORTS = 1024
 MAX_SLABS = 8
 ABI_VERSION = 2          # the header's SGV_ABI_VERSION this binding is typed against
 TIMERS_N, EXCHANGE_STATS_N, COMM_INFO_N = 10, 16, 5
+
+# sgv_ld_pass_form / sgv_pass_form_model (the header's SGV_KIND_*, SGV_PF_*, SGV_PS_*, SGV_SW_*,
+# in index order): the kinds by value, the form's fields, the shape's, the switches
+PASS_KINDS = ("none", "valu", "strip4", "pair", "wide", "strip16", "walk")
+PASS_FORM_FIELDS = ("kind", "valu_class", "rest_kind", "load_form", "fin_form", "pk_width",
+                    "pk_paired", "dense", "side", "rest_side", "mfma16", "idle_exit")
+PLAN_SHAPE_FIELDS = ("bits", "dense", "packed", "walks", "wide", "rest", "ragged", "pair",
+                     "rest_ragged", "rest_pair", "wide_idle", "ngrp", "wide_ngrp", "rest_ngrp")
+PASS_SWITCHES = ("SGV_BAND_WALK", "SGV_F32_WALK", "SGV_MF_WIDE", "SGV_MF_PAIR",
+                 "SGV_MF_WIDE_IDLE", "SGV_F32_FORM", "SGV_FIN_FORM")
+PassForm = collections.namedtuple("PassForm", PASS_FORM_FIELDS)
 
 _c_int_p = ctypes.POINTER(ctypes.c_int)
 _c_i64_p = ctypes.POINTER(ctypes.c_int64)
@@ -118,6 +130,9 @@ _SIGS = {
     "sgv_step_end": [_vp],
     "sgv_probe_draw": [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32),
                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _c_i8_p],
+    "sgv_ld_pass_form": [_vp, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int],
+    "sgv_pass_form_model": [_c_int_p, _c_int_p, ctypes.c_int, ctypes.c_int, _c_int_p,
+                            ctypes.c_int],
     "sgv_sync": [_vp],
     "sgv_read_bw": [_vp, ctypes.c_int64, ctypes.c_int, _c_dbl_p],
 }
@@ -169,6 +184,33 @@ def load(path=LIB_PATH, strict=True):
                        "`make -C sgvamp-py_amd/csrc`" % (path, lib.sgv_abi_version(), ABI_VERSION))
     _lib = lib
     return lib
+
+
+def pass_form_of(ints):
+    """The ints of sgv_ld_pass_form / sgv_pass_form_model as a PassForm: the kinds
+    by name, the flags as bools."""
+    v = [int(x) for x in ints]
+    named = {"kind": PASS_KINDS[v[0]], "rest_kind": PASS_KINDS[v[2]]}
+    flags = ("pk_paired", "dense", "side", "rest_side", "mfma16", "idle_exit")
+    return PassForm(*[named.get(f, bool(x) if f in flags else x)
+                      for f, x in zip(PASS_FORM_FIELDS, v)])
+
+
+def pass_form_model(shape, switches, mfma_min, ncol):
+    """sgv_pass_form_model (host arithmetic, no device): the form a pass of ncol
+    columns takes over a plan of `shape` (PLAN_SHAPE_FIELDS by name; absent: bits
+    64, wide_idle and the group counts 1, else 0) under `switches` (PASS_SWITCHES
+    by name -> value; absent: unset)."""
+    dflt = {"bits": 64, "wide_idle": 1, "ngrp": 1, "wide_ngrp": 1, "rest_ngrp": 1}
+    assert set(shape) <= set(PLAN_SHAPE_FIELDS) and set(switches) <= set(PASS_SWITCHES)
+    sh = np.array([int(shape.get(f, dflt.get(f, 0))) for f in PLAN_SHAPE_FIELDS], dtype=np.int32)
+    sw = np.array([int(switches.get(n, -1)) for n in PASS_SWITCHES], dtype=np.int32)
+    out = np.zeros(len(PASS_FORM_FIELDS), dtype=np.int32)
+    rc = load().sgv_pass_form_model(iptr(sh), iptr(sw), int(mfma_min), int(ncol), iptr(out),
+                                    len(out))
+    if rc != SGV_OK:
+        raise HipError("sgv_pass_form_model failed (%d)" % rc)
+    return pass_form_of(out)
 
 
 FSOLVE_FN = ctypes.CFUNCTYPE(ctypes.c_int, _vp, ctypes.c_int, _c_dbl_p, _c_dbl_p)

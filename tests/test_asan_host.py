@@ -1,8 +1,10 @@
 """The library's host-only code (csrc/hybrd.cpp: fsolve's MINPACK hybrd as
-scipy drives it; csrc/probes.cpp: the MT19937 binomial probe stream) under
+scipy drives it; csrc/probes.cpp: the MT19937 binomial probe stream;
+csrc/pass_form.cpp: the LD pass's form decision) under
 AddressSanitizer + UndefinedBehaviorSanitizer: tools/asan_host.cpp drives
-fsolve on converging, stalling, rootless and user-stopped systems and the
-probe stream in split / whole draws at even and odd stream positions.  GPU
+fsolve on converging, stalling, rootless and user-stopped systems, the
+probe stream in split / whole draws at even and odd stream positions, and
+pass_form over the product of tests/test_pass_form.py.  GPU
 code cannot be sanitized on this pool; this covers the host code
 the GPU path calls.  CPU only."""
 import os
@@ -24,7 +26,7 @@ def test_host_code_under_asan_ubsan(tmp_path):
            "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
            "-I" + os.path.join(ROOT, "include"), "-I" + csrc,
            os.path.join(ROOT, "tools", "asan_host.cpp"), os.path.join(csrc, "hybrd.cpp"),
-           os.path.join(csrc, "probes.cpp"), "-o", exe]
+           os.path.join(csrc, "probes.cpp"), os.path.join(csrc, "pass_form.cpp"), "-o", exe]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     if b.returncode != 0 and "asan" in b.stderr.lower():
         pytest.skip("sanitizer runtime unavailable: " + b.stderr[-300:])

@@ -94,6 +94,16 @@ def environ(env):
                 os.environ[k] = old[k]
 
 
+def assert_strips(eng, ncol, bits, env):
+    """The next ncol-column pass reports what every arm of this file claims: the
+    4-wave 512-column strips (the 16x16x4 ones above 8 columns) in the arm's load
+    form -- an f32 matrix the 16-B form unless SGV_F32_FORM=1, an f64 one the 8-B."""
+    form = eng.ld_pass_form(0, ncol)
+    lf = 1 if bits == 64 or (env or {}).get("SGV_F32_FORM") == "1" else 2
+    assert (form.kind, form.load_form) == ("strip4" if ncol <= 8 else "strip16", lf), (
+        ncol, bits, env, form)
+
+
 def products(sizes, ncols, bits=32, env=None, repeat=1, mfma_min=None, widen=False, checks=None):
     """{ncol: [Y, ...]}: `repeat` products per column count on a fresh engine
     holding block(n) (widen: W(block(n))) for n in sizes at `bits`; checks(eng)
@@ -109,6 +119,7 @@ def products(sizes, ncols, bits=32, env=None, repeat=1, mfma_min=None, widen=Fal
         out = {}
         for ncol in ncols:
             V = rhs(sizes, ncol)
+            assert_strips(eng, ncol, bits, env)
             out[ncol] = [np.array(eng.ld_matvec(0, V)) for _ in range(repeat)]
         if checks:
             checks(eng)
@@ -233,6 +244,8 @@ def band_products(bits, ncols, env=None, widen=False, mfma_min=None):
         info["prec"] = [eng.ld_block_precision(0, b) for b in range(2)]
         eng.set_ridge(RIDGE)
         for ncol in ncols:
+            assert_strips(eng, ncol, bits, env)
+            assert eng.ld_pass_form(0, ncol).fin_form == (1 if ncol <= 8 else 4)   # ragged strips
             out[ncol] = np.array(eng.ld_matvec(0, rhs([nb, 1281], ncol)))
         info["band"] = eng.get_ld_block(0, 0)
         eng.close()

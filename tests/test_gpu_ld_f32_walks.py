@@ -37,8 +37,9 @@ from engine import Engine
 from oracle import vamp_oracle as vo
 from sgvamp import VAMP, BlockLD
 from tests import exact_ld as xl
-from tests.test_gpu_pass_exact import (ALL, call, data, epilogue_gate, expect, nan_cols, nan_gate,
-                                       two_matrix_engine, upload, OUT_FILL, YOUT_FILL)
+from tests.test_gpu_pass_exact import (ALL, assert_form, call, data, epilogue_gate, expect, kinds,
+                                       nan_cols, nan_gate, two_matrix_engine, upload, OUT_FILL,
+                                       YOUT_FILL)
 from tests.test_gpu_pass_exact import environ as pass_environ
 
 pytestmark = pytest.mark.gpu
@@ -70,20 +71,25 @@ def environ(env):
 def assert_walks(eng, ld, M, ncol=4):
     """An ncol-column pass of LD matrix ld takes the walks: its partial traffic
     (sgv_timers t[5]) is not what the same pass moves on the strips
-    (SGV_BAND_WALK=0, read per pass).  Called under SGV_AB=1."""
+    (SGV_BAND_WALK=0, read per pass) -- the evidence, independent of the report,
+    that the form Engine.ld_pass_form reports beside it is the one that ran.
+    Called under SGV_AB=1."""
     def aux():
         eng.timers(reset=True)
         eng.ld_matvec(ld, np.zeros((ncol, M)))
         return eng.timers()["aux_bytes"]
 
     assert os.environ.get("SGV_AB") == "1" and "SGV_BAND_WALK" not in os.environ
+    assert eng.ld_pass_form(ld, ncol).kind == "walk", (ld, ncol, eng.ld_pass_form(ld, ncol))
     walked = aux()
     os.environ["SGV_BAND_WALK"] = "0"
     try:
+        assert eng.ld_pass_form(ld, ncol).kind in ("strip4", "pair"), eng.ld_pass_form(ld, ncol)
         strips = aux()
     finally:
         del os.environ["SGV_BAND_WALK"]
     assert walked != strips, (ld, ncol, walked, strips)
+    assert eng.ld_pass_form(ld, ncol).kind == "walk"
     assert aux() == walked
 
 
@@ -138,7 +144,8 @@ def rhs(M, ncol):
 
 
 def run(blocks, ncols, bits=32, env=None, widen=False, mfma_min=None, key=None):
-    """{ncol: ([Y, Y again], aux_bytes of the second pass)} on a fresh band-only
+    """{ncol: ([Y, Y again], aux_bytes of the second pass, the form reported
+    before the first)} on a fresh band-only
     engine holding `blocks` (widen: their widened copies) at `bits`; cached
     under key."""
     if key is not None and key in _runs:
@@ -155,10 +162,11 @@ def run(blocks, ncols, bits=32, env=None, widen=False, mfma_min=None, key=None):
             assert eng.ld_block_format(0, b) == 2 and eng.ld_block_precision(0, b) == bits
         for ncol in ncols:
             V = rhs(sum(sizes), ncol)
+            form = eng.ld_pass_form(0, ncol)
             Y = [np.array(eng.ld_matvec(0, V))]
             eng.timers(reset=True)
             Y.append(np.array(eng.ld_matvec(0, V)))
-            out[ncol] = (Y, eng.timers()["aux_bytes"])
+            out[ncol] = (Y, eng.timers()["aux_bytes"], form)
         eng.close()
     if key is not None:
         _runs[key] = out
@@ -192,6 +200,13 @@ def test_f32_walk_selection(bw):
     for n in nc:
         print("bw=%d ncol=%d aux bytes: f32 walks %.0f f64 %.0f strips %.0f shipped f32 %.0f" % (
             bw, n, f32[n][1], f64[n][1], f64_strips[n][1], shipped[n][1]))
+        # the reported forms (bw = 300 and 1,000: the band's strips are ragged)
+        assert (f32[n][2].kind, f32[n][2].load_form) == ("walk", int(SHIPPED_FORM)), f32[n][2]
+        assert (f64[n][2].kind, f64[n][2].load_form) == ("walk", 1), f64[n][2]
+        assert (f32_valu[n][2].kind, f32_valu[n][2].load_form) == ("walk", int(SHIPPED_FORM))
+        assert f32_strips[n][2].kind == f64_strips[n][2].kind == shipped[n][2].kind == "strip4", n
+        assert (f32_strips[n][2].fin_form, f64_strips[n][2].fin_form) == (1, 1), n
+        # and the traffic that bears them out
         assert f32[n][1] == f64[n][1], n
         assert f32[n][1] != f64_strips[n][1], n
         assert f32_strips[n][1] == f64_strips[n][1], n
@@ -199,6 +214,8 @@ def test_f32_walk_selection(bw):
         np.testing.assert_array_equal(f32_valu[n][0][0], f32[n][0][0])
         assert not np.array_equal(f32[n][0][0], f32_strips[n][0][0])
     for n in STRIP_NCOLS:
+        for r in (f32, f32_strips, shipped):
+            assert r[n][2].kind == ("strip4" if n <= 8 else "strip16"), (n, r[n][2])
         np.testing.assert_array_equal(f32[n][0][0], f32_strips[n][0][0])
     for n in nc + STRIP_NCOLS:
         if n in DEFAULT_WALK_NCOLS:
@@ -222,6 +239,8 @@ def test_f32_walk_8B_form_bitwise_the_f64_walks_on_widened_blocks(bw):
     dflt = walked_f32(bw)
     assert not np.array_equal(W(B[0].data), B[0].data)          # the rounding is real
     for n in WALK_NCOLS:
+        assert [(r[n][2].kind, r[n][2].load_form) for r in (form1, pin, forced, dflt)] == [
+            ("walk", 1), ("walk", 1), ("walk", int(SHIPPED_FORM)), ("walk", int(SHIPPED_FORM))], n
         np.testing.assert_array_equal(form1[n][0][0], pin[n][0][0])
         np.testing.assert_array_equal(dflt[n][0][0], forced[n][0][0])
         assert not np.array_equal(dflt[n][0][0], form1[n][0][0])    # another summation order
@@ -290,10 +309,11 @@ def test_f32_walk_forms_exact(bw):
     and the 16-B form beside it (test_band_forms_exact[f32-*] holds what ships:
     the strips)."""
     dn, dw = data(("walk", bw), "narrow"), data(("walk", bw), "wide")
-    for tag, env in (("f32_8B", FORM1), ("f32_16B", WALK)):
+    for tag, env, lf in (("f32_8B", FORM1, 1), ("f32_16B", WALK, 2)):
         with environ(env):
             eng = two_matrix_engine(dn, dw, lambda e: e.set_ld_precision(32), 2, 32)
-            epilogue_gate(eng, dn, dw, ALL, (tag, bw))
+            # 1-2 columns on the strips, 3-8 on the walks, 9-16 on the 16x16x4 strips
+            epilogue_gate(eng, dn, dw, ALL, (tag, bw), kinds("strip4", "walk", load_form=lf))
             nan_gate(eng, dn, nan_cols(ALL), (tag, bw))
             for ld in (0, 1):
                 assert_walks(eng, ld, dn.M)
@@ -324,7 +344,7 @@ def test_f32_coupled_pieces_exact():
                 assert eng.ld_block_format(ld, b) == 2 and eng.ld_block_precision(ld, b) == 32
             for gb, (nr, nc, C) in cpl.items():
                 eng.set_ld_coupling(ld, gb, nr, nc, C)
-        epilogue_gate(eng, dn, dw, ncols, "f32 coupled")
+        epilogue_gate(eng, dn, dw, ncols, "f32 coupled", kinds("strip4", "walk", load_form=2))
         nan_gate(eng, dn, nan_cols(ncols), "f32 coupled")
         for ld in (0, 1):
             assert_walks(eng, ld, dn.M)
@@ -354,6 +374,8 @@ def test_history_independence_across_element_types():
             run_ = int(rs.choice([-1, -1, 1, 0]))
             w = "alias" if rs.randint(2) else band.W[:ncol]
             c1, c2 = xl.narrow_coeffs(ncol)
+            assert_form(eng, ld, ncol, (kinds("valu", "walk", load_form=1),
+                                        kinds("strip4", "walk", load_form=2))[ld], ("history", step))
             got = call(eng, ld, band, ncol, c1, c2, w if dm else None, dm, ym, run=run_)
             tag = ("history", step, ld, ncol, hex(dm), hex(ym), run_)
             if run_ == 0:

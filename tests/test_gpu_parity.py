@@ -725,6 +725,8 @@ def test_mfma_pair_kernel_bitwise(strip, monkeypatch):
         out[form] = {}
         for ncol in range(3, 9):
             V = np.random.RandomState(ncol).normal(size=(ncol, sum(sizes)))
+            assert eng.ld_pass_form(0, ncol).kind == ("pair" if form == "1" else "strip4"), (
+                form, ncol, eng.ld_pass_form(0, ncol))
             out[form][ncol] = eng.ld_matvec(0, V)
         eng.close()
     for ncol in range(3, 9):
@@ -863,6 +865,11 @@ def test_finalize_forms_bitwise(monkeypatch):
         for b in range(len(L.block_sizes)):
             L.upload(eng, 0, b)
         assert {eng.ld_block_format(0, b) for b in range(len(L.block_sizes))} == {1, 2}
+        # the triangle wide with the bands' strips behind it, or every block on 16x16x4
+        for nc in (3, 5, 8, 11, 16):
+            f = eng.ld_pass_form(0, nc)
+            want = ("wide", "strip4") if nc <= 8 else ("strip16", "none")
+            assert (f.kind, f.rest_kind, f.fin_form) == want + (int(form),), (form, nc, f)
         out[form] = [eng.ld_matvec(0, np.random.RandomState(nc).normal(size=(nc, A.shape[0])))
                      for nc in (3, 5, 8, 11, 16)]
         eng.close()

@@ -6,6 +6,11 @@ summation order, FMA contraction or storage -- must equal ONE integer reference
 bit for bit: out, the carried yout and the panel dots, through
 Engine.ld_pass_ex (sgv_ld_pass_ex: the whole PassArgs, the dots through the
 CG's ordered reduction).  No tolerance appears in this file.
+
+Every form names the kernel form it expects per column count, and the gate
+asserts Engine.ld_pass_form against it before the passes: a switch that
+silently fell back to another form would leave every product right and the
+form uncovered.
 """
 import contextlib
 import os
@@ -130,10 +135,39 @@ def expect(d, ncol, c1, c2, w, dot_mask, yout_mask, tag, got):
             assert got[2][j] == dots[j], ("dot", tag, j, got[2][j], dots[j])
 
 
-def epilogue_gate(eng, dn, dw, ncols, tag, ld_n=0, ld_w=1):
-    """Every column count of one form on one engine: the narrow-regime epilogue
-    calls (out, yout, dots), the wide-bit call (out), the two run calls."""
+def kinds(small, mid, **more):
+    """ncol -> the PassForm fields a form expects: the packed kind `small` at 1-2
+    columns, `mid` at 3-8, the 16x16x4 strips above; `more` at every count."""
+    return lambda n: dict(kind=small if n <= 2 else mid if n <= 8 else "strip16", **more)
+
+
+def assert_form(eng, ld, ncol, want, tag):
+    """The form the next pass of ncol columns over ld reports is `want`(ncol),
+    with what follows from the kind: the VALU class, the Pk layout of an MFMA
+    pass, the 9-16-column counter flag, no finalize form without strip finalize."""
+    f = eng.ld_pass_form(ld, ncol)
+    w = dict(want(ncol))
+    if w["kind"] == "valu":
+        w.update(valu_class=0 if ncol <= 2 else 1 if ncol <= 4 else 2 if ncol <= 8 else 3,
+                 pk_width=0, load_form=0, fin_form=0)
+    elif w["kind"] != "none":
+        w.update(pk_width=4 if ncol <= 4 else 8 if ncol <= 8 else 16, pk_paired=4 < ncol <= 8)
+    w.setdefault("mfma16", w["kind"] == "strip16")
+    if w["kind"] == "wide":
+        w.setdefault("idle_exit", True)
+    else:
+        w.setdefault("rest_kind", "none")
+    got = {k: getattr(f, k) for k in w}
+    assert got == w, (tag, ld, ncol, f)
+
+
+def epilogue_gate(eng, dn, dw, ncols, tag, want, ld_n=0, ld_w=1):
+    """Every column count of one form on one engine: the reported form, then the
+    narrow-regime epilogue calls (out, yout, dots), the wide-bit call (out), the
+    two run calls."""
     for ncol in ncols:
+        for ld in (ld_n, ld_w):
+            assert_form(eng, ld, ncol, want, tag)
         full = (1 << ncol) - 1
         c1, c2 = xl.narrow_coeffs(ncol)
         W = dn.W[:ncol]
@@ -210,19 +244,35 @@ def two_matrix_engine(dn, dw, setup=None, fmt=None, bits=None):
 # ---- triangle, dense and f32 geometry ---------------------------------------
 ALL = list(range(1, 17))
 TRI_FORMS = {
-    # name: (A/B switches, engine setup, columns, data kind, blocks kept, format, stored bits)
-    "default": ({}, None, ALL, "tri", None, 1, 64),
-    "valu": ({}, lambda e: e.set_mfma_min(0), ALL, "tri", None, 1, 64),
+    # name: (A/B switches, engine setup, columns, data kind, blocks kept, format, stored bits,
+    #        the form expected per column count)
+    # triangles: no strip is ragged (finalize 4); the wide form has no strip finalize
+    "default": ({}, None, ALL, "tri", None, 1, 64,
+                kinds("valu", "wide", load_form=1, dense=False)),
+    "valu": ({}, lambda e: e.set_mfma_min(0), ALL, "tri", None, 1, 64,
+             lambda n: dict(kind="valu")),
     "strips4": ({"SGV_MF_WIDE": "0", "SGV_MF_PAIR": "0"}, None, list(range(3, 17)), "tri", None,
-                1, 64),
-    "pair": ({"SGV_MF_PAIR": "1"}, None, list(range(3, 9)), "tri", None, 1, 64),
-    "wide": ({"SGV_MF_WIDE": "1"}, None, list(range(3, 9)), "tri", None, 1, 64),
-    "dense": ({}, lambda e: e.set_ld_packing(False), ALL, "tri", len(xl.DENSE_SIZES), 0, 64),
-    "nonsym": ({}, None, ALL, "nonsym", None, lambda n: 0 if n > 1 else 1, 64),
-    "f32_16B": ({}, lambda e: e.set_ld_precision(32), ALL, "tri", None, 1, 32),
-    "f32_8B": ({"SGV_F32_FORM": "1"}, lambda e: e.set_ld_precision(32), ALL, "tri", None, 1, 32),
-    "fin1": ({"SGV_FIN_FORM": "1"}, None, list(range(3, 17)), "mixed", None, None, 64),
-    "fin4": ({"SGV_FIN_FORM": "4"}, None, list(range(3, 17)), "mixed", None, None, 64),
+                1, 64, kinds("valu", "strip4", load_form=1, fin_form=4)),
+    "pair": ({"SGV_MF_PAIR": "1"}, None, list(range(3, 9)), "tri", None, 1, 64,
+             kinds("valu", "pair", load_form=1, fin_form=4)),
+    "wide": ({"SGV_MF_WIDE": "1"}, None, list(range(3, 9)), "tri", None, 1, 64,
+             kinds("valu", "wide", load_form=1, fin_form=0, rest_kind="none")),
+    "dense": ({}, lambda e: e.set_ld_packing(False), ALL, "tri", len(xl.DENSE_SIZES), 0, 64,
+              lambda n: dict(kind="none", dense=True)),
+    # the block of one marker is symmetric, so packed: it runs as a triangle beside the squares
+    "nonsym": ({}, None, ALL, "nonsym", None, lambda n: 0 if n > 1 else 1, 64,
+               kinds("valu", "wide", dense=True)),
+    "f32_16B": ({}, lambda e: e.set_ld_precision(32), ALL, "tri", None, 1, 32,
+                kinds("strip4", "strip4", load_form=2, fin_form=4)),
+    "f32_8B": ({"SGV_F32_FORM": "1"}, lambda e: e.set_ld_precision(32), ALL, "tri", None, 1, 32,
+               kinds("strip4", "strip4", load_form=1, fin_form=4)),
+    # mixed: the triangles wide, the band blocks' ragged 512-column strips behind them
+    "fin1": ({"SGV_FIN_FORM": "1"}, None, list(range(3, 17)), "mixed", None, None, 64,
+             lambda n: dict(kinds("valu", "wide", fin_form=1)(n),
+                            **({"rest_kind": "strip4"} if n <= 8 else {}))),
+    "fin4": ({"SGV_FIN_FORM": "4"}, None, list(range(3, 17)), "mixed", None, None, 64,
+             lambda n: dict(kinds("valu", "wide", fin_form=4)(n),
+                            **({"rest_kind": "strip4"} if n <= 8 else {}))),
 }
 
 
@@ -231,7 +281,7 @@ def test_triangle_forms_exact(form):
     """Every pass form over dense-triangle, full-square and f32 storage, each at
     all of its column counts on one engine holding TRI_SIZES (the full-square
     forms without 8449; the finalize forms on a plan mixing bands and triangles)."""
-    env, setup, ncols, kind, keep, fmt, bits = TRI_FORMS[form]
+    env, setup, ncols, kind, keep, fmt, bits, want = TRI_FORMS[form]
     dn, dw = data(kind, "narrow"), data(kind, "wide")
     if keep is not None:
         dn, dw = dn.prefix(keep), dw.prefix(keep)
@@ -239,17 +289,46 @@ def test_triangle_forms_exact(form):
         eng = two_matrix_engine(dn, dw, setup, fmt, bits)
         if kind == "mixed":
             assert {eng.ld_block_format(0, b) for b in range(len(dn.sizes))} == {1, 2}
-        epilogue_gate(eng, dn, dw, ncols, form)
+        epilogue_gate(eng, dn, dw, ncols, form, want)
         nan_gate(eng, dn, nan_cols(ncols), form)
         eng.close()
 
 
 # ---- band geometry: walks, band strips, VALU, f32 ---------------------------
+# bw -> are the band's 512-column strips ragged: a panel stores round_up(256 + bw,
+# 256) columns -- 512 or 1,024 at bw = 200 / 600, whole 512-column items; 768 or
+# 1,280 at bw = 300 / 1,000, whose strips end in a 256-column item
+BAND_RAGGED = {200: False, 300: True, 600: False, 1000: True}
+
+
+def band_strips(bw, small, **more):
+    """The band strips' form: the ragged set takes the 4-wave kernel and, up to 8
+    columns, finalize 1; the even set the kernel of the launch-tail model
+    (BAND_STRIPS_EVEN) and finalize 4."""
+    def want(n):
+        w = kinds(small, "strip4" if BAND_RAGGED[bw] else BAND_STRIPS_EVEN, **more)(n)
+        if w["kind"] != "valu":
+            w["fin_form"] = 1 if BAND_RAGGED[bw] and n <= 8 else 4
+        return w
+    return want
+
+
+# walk_sizes(200) and walk_sizes(600) make fewer strips than either strip kernel
+# has slots on the 256 CUs of an MI355X, so the tail model (ldplan.hip
+# mfma_pair_choice) sees the pair kernel's 256 slots twice as well filled as the
+# 4-wave kernel's 512, far above its 3 % margin: the "strips" arm of these two
+# runs the wave-pair strips, that of bw = 300 and 1,000 the 4-wave ones
+BAND_STRIPS_EVEN = "pair"
 BAND_FORMS = {
-    "walks": ({}, None, ALL),          # 1-2 VALU, 3-8 the walks, 9-16 the band strips
-    "strips": ({"SGV_BAND_WALK": "0"}, None, ALL),
-    "valu": ({}, lambda e: e.set_mfma_min(0), ALL),
-    "f32": ({}, lambda e: e.set_ld_precision(32), ALL),
+    # 1-2 VALU, 3-8 the walks, 9-16 the band strips
+    "walks": ({}, None, ALL, lambda bw: kinds("valu", "walk", load_form=1)),
+    "strips": ({"SGV_BAND_WALK": "0"}, None, ALL,
+               lambda bw: band_strips(bw, "valu", load_form=1)),
+    "valu": ({}, lambda e: e.set_mfma_min(0), ALL, lambda bw: lambda n: dict(kind="valu")),
+    # SGV_F32_WALK set in the shell fails here: the 3-8-column passes would report the walks
+    "f32": ({}, lambda e: e.set_ld_precision(32), ALL,
+            lambda bw: lambda n: dict(band_strips(bw, "strip4", load_form=2)(n),
+                                      kind="strip4" if n <= 8 else "strip16")),
 }
 
 
@@ -260,11 +339,11 @@ def test_band_forms_exact(form, bw):
     2..5: P = R + 1 .. 2 W + 2 panels with ragged, half and whole last panels --
     blocks shorter than a walk, exactly W, W + 1 and 2 W panels, trailing walks
     of 1 .. R - 2 panels, single carry slots."""
-    env, setup, ncols = BAND_FORMS[form]
+    env, setup, ncols, want = BAND_FORMS[form]
     dn, dw = data(("walk", bw), "narrow"), data(("walk", bw), "wide")
     with environ(env):
         eng = two_matrix_engine(dn, dw, setup, 2, 32 if form == "f32" else 64)
-        epilogue_gate(eng, dn, dw, ncols, (form, bw))
+        epilogue_gate(eng, dn, dw, ncols, (form, bw), want(bw))
         nan_gate(eng, dn, nan_cols(ncols), (form, bw))
         eng.close()
 
@@ -294,7 +373,8 @@ def test_coupled_pieces_exact():
                 assert eng.ld_block_format(ld, b) == 2
             for gb, (nr, nc, C) in cpl.items():
                 eng.set_ld_coupling(ld, gb, nr, nc, C)
-        epilogue_gate(eng, dn, dw, ncols, "coupled")
+        # band pieces only: 1-2 VALU, 3-8 the walks, 16 the band strips
+        epilogue_gate(eng, dn, dw, ncols, "coupled", kinds("valu", "walk", load_form=1))
         nan_gate(eng, dn, nan_cols(ncols), "coupled")
         eng.close()
 
@@ -317,6 +397,8 @@ def test_history_independence():
         for b in range(len(xl.HIST_SIZES)):
             assert [eng.ld_block_format(ld, b) for ld in range(3)] == [1, 2, 1]
             assert [eng.ld_block_precision(ld, b) for ld in range(3)] == [64, 64, 32]
+        want = [kinds("valu", "wide", load_form=1), kinds("valu", "walk", load_form=1),
+                kinds("strip4", "strip4", load_form=2, fin_form=4)]
         rs = np.random.RandomState(2024)
         # every (matrix, column count) cell once in a shuffled order, then 24 more
         cells = list(rs.permutation(48)) + list(rs.randint(48, size=24))
@@ -328,6 +410,7 @@ def test_history_independence():
             w = "alias" if rs.randint(2) else per_ld[ld].W[:ncol]
             c1, c2 = xl.narrow_coeffs(ncol)
             d = per_ld[ld]
+            assert_form(eng, ld, ncol, want[ld], ("history", step))
             got = call(eng, ld, d, ncol, c1, c2, w if dm else None, dm, ym, run=run)
             tag = ("history", step, ld, ncol, hex(dm), hex(ym), run)
             if run == 0:

@@ -70,9 +70,10 @@ def environ(env):
                 os.environ[k] = old[k]
 
 
-def products(sizes, ncols, env, repeat=1):
+def products(sizes, ncols, env, repeat=1, kinds=("wide",)):
     """{ncol: [Y, ...]}: `repeat` products per column count on a fresh engine
-    holding block(n) for n in sizes, under the A/B switches `env`."""
+    holding block(n) for n in sizes, under the A/B switches `env`; every pass
+    reports one of the packed `kinds` up to 8 columns, the 16x16x4 strips above."""
     with environ(env):
         eng = Engine(sizes, K=1)
         for b, n in enumerate(sizes):
@@ -81,6 +82,9 @@ def products(sizes, ncols, env, repeat=1):
         out = {}
         for ncol in ncols:
             V = np.concatenate([vec(n, ncol) for n in sizes], axis=1)
+            form = eng.ld_pass_form(0, ncol)
+            assert form.kind in (kinds if ncol <= 8 else ("strip16",)), (env, ncol, form)
+            assert form.idle_exit == (form.kind == "wide"), form
             out[ncol] = [np.array(eng.ld_matvec(0, V)) for _ in range(repeat)]
         eng.close()
     return out
@@ -126,7 +130,8 @@ def test_wide_default_selection():
     sizes = [2600, 1281]
     default = products(sizes, [8, 16], {})
     wide = products(sizes, [8], FORCED)
-    narrow = products(sizes, [8, 16], {"SGV_AB": "1", "SGV_MF_WIDE": "0"})
+    narrow = products(sizes, [8, 16], {"SGV_AB": "1", "SGV_MF_WIDE": "0"},
+                      kinds=("strip4", "pair"))   # either 512-column kernel: bitwise one product
     np.testing.assert_array_equal(default[8][0], wide[8][0])
     np.testing.assert_array_equal(default[16][0], narrow[16][0])
     assert not np.array_equal(wide[8][0], narrow[8][0])
@@ -159,6 +164,8 @@ def test_wide_beside_band_block():
         eng.set_ld_block(0, 1, block(1281))
         assert eng.ld_block_format(0, 0) == 2 and eng.ld_block_format(0, 1) == 1
         eng.set_ridge(RIDGE)
+        form = eng.ld_pass_form(0, ncol)   # the band's strips are ragged: 4-wave, finalize 1
+        assert (form.kind, form.rest_kind, form.fin_form) == ("wide", "strip4", 1), form
         Y = np.array(eng.ld_matvec(0, V))
         eng.close()
     L = vo.BlockLD([band, block(1281)], s=RIDGE)

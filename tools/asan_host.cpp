@@ -1,7 +1,9 @@
 // Host-side sanitizer run of the library's host-only code (tests/test_asan_host.py):
-// csrc/hybrd.cpp (the fsolve restatement) and csrc/probes.cpp (the MT19937
-// binomial probe stream) built with -fsanitize=address,undefined and driven on
-// a few systems and on split / whole probe draws.  GPU code is out of reach of
+// csrc/hybrd.cpp (the fsolve restatement), csrc/probes.cpp (the MT19937
+// binomial probe stream) and csrc/pass_form.cpp (the LD pass's form decision)
+// built with -fsanitize=address,undefined and driven on a few systems, on
+// split / whole probe draws and over the whole product of plan shapes, column
+// counts and switch settings.  GPU code is out of reach of
 // the sanitizers on this pool; this covers the host code the GPU tests call.
 #include <cmath>
 #include <cstdint>
@@ -9,6 +11,7 @@
 #include <cstring>
 #include <vector>
 
+#include "pass_form.h"
 #include "sgvamp_hip.h"
 
 extern "C" int sgv_probe_draw(uint32_t* key, int32_t* pos, int64_t n, int64_t lo, int64_t hi,
@@ -106,6 +109,73 @@ int main() {
     bad += sgv_probe_draw(k, &p, 4, 3, 2, o) == 0;
     bad += sgv_probe_draw(k, &p, 4, 0, 5, o) == 0;
     bad += sgv_probe_draw(nullptr, &p, 4, 0, 4, o) == 0;
+  }
+  {   // pass_form over the product tests/test_pass_form.py sweeps, through the model's ints:
+      // every form inside its ranges, the direct call and the model agree
+    const int sv[SGV_SW_N][3] = {{-1, 0, 0}, {-1, 1, 1}, {-1, 0, 1}, {-1, 0, 1},
+                                 {-1, 0, 0}, {-1, 1, 2}, {-1, 1, 4}};
+    const int sn[SGV_SW_N] = {2, 2, 3, 3, 2, 3, 3};
+    long n_forms = 0;
+    for (int bits : {64, 32})
+      for (int mm : {0, 1, 3, 9})
+        for (int nc = 1; nc <= 16; ++nc)
+          for (int shape_bits = 0; shape_bits < 16 * 3; ++shape_bits) {
+            int32_t sh[SGV_PS_N] = {};
+            sh[SGV_PS_BITS] = bits;
+            sh[SGV_PS_PACKED] = 1;
+            sh[SGV_PS_WALKS] = shape_bits & 1;
+            sh[SGV_PS_WIDE] = shape_bits >> 1 & 1;
+            sh[SGV_PS_REST] = shape_bits >> 2 & 1;
+            sh[SGV_PS_RAGGED] = sh[SGV_PS_REST_RAGGED] = shape_bits >> 3 & 1;
+            sh[SGV_PS_PAIR] = sh[SGV_PS_REST_PAIR] = shape_bits >> 4;
+            sh[SGV_PS_WIDE_IDLE] = sh[SGV_PS_NGRP] = sh[SGV_PS_WIDE_NGRP] = sh[SGV_PS_REST_NGRP] = 1;
+            int ix[SGV_SW_N] = {};
+            for (bool more = true; more;) {
+              int32_t sw[SGV_SW_N], form[SGV_PF_N + 1];
+              for (int i = 0; i < SGV_SW_N; ++i) sw[i] = sv[i][ix[i]];
+              form[SGV_PF_N] = -7;
+              bad += sgv_pass_form_model(sh, sw, mm, nc, form, SGV_PF_N + 1) != SGV_OK;
+              bad += form[SGV_PF_N] != -7;
+              const int k = form[SGV_PF_KIND];
+              bad += k < SGV_KIND_VALU || k > SGV_KIND_WALK;
+              bad += (k == SGV_KIND_VALU) != (form[SGV_PF_PK_WIDTH] == 0);
+              bad += k != SGV_KIND_VALU && nc > form[SGV_PF_PK_WIDTH];
+              bad += (k == SGV_KIND_VALU) != (form[SGV_PF_VALU_CLASS] >= 0);
+              bad += form[SGV_PF_VALU_CLASS] > 3;
+              bad += (k == SGV_KIND_WALK || k == SGV_KIND_WIDE || k == SGV_KIND_PAIR) && nc > 8;
+              bad += k == SGV_KIND_WIDE && nc < 3;
+              bad += form[SGV_PF_REST_KIND] != SGV_KIND_NONE && k != SGV_KIND_WIDE;
+              sgv::PlanShape ps;
+              ps.bits = bits;
+              ps.packed = true;
+              ps.walks = sh[SGV_PS_WALKS];
+              ps.wide = sh[SGV_PS_WIDE];
+              ps.rest = sh[SGV_PS_REST];
+              ps.ragged = ps.rest_ragged = sh[SGV_PS_RAGGED];
+              ps.pair = ps.rest_pair = sh[SGV_PS_PAIR];
+              sgv::PassSwitches s;
+              s.band_walk = sw[0], s.f32_walk = sw[1], s.mf_wide = sw[2], s.mf_pair = sw[3];
+              s.mf_wide_idle = sw[4], s.f32_form = sw[5], s.fin_form = sw[6];
+              int32_t direct[SGV_PF_N];
+              sgv::pass_form_ints(sgv::pass_form(ps, nc, mm, s), direct, SGV_PF_N);
+              bad += std::memcmp(direct, form, sizeof direct) != 0;
+              ++n_forms;
+              more = false;
+              for (int i = 0; i < SGV_SW_N && !more; ++i) {
+                more = ++ix[i] < sn[i];
+                if (!more) ix[i] = 0;
+              }
+            }
+          }
+    std::printf("pass forms %ld\n", n_forms);
+    bad += n_forms != 2L * 4 * 16 * 48 * 648;
+    int32_t sh[SGV_PS_N] = {64}, sw[SGV_SW_N] = {-1, -1, -1, -1, -1, -1, -1}, form[SGV_PF_N];
+    bad += sgv_pass_form_model(sh, sw, 3, 0, form, SGV_PF_N) == SGV_OK;
+    bad += sgv_pass_form_model(sh, sw, 3, 17, form, SGV_PF_N) == SGV_OK;
+    bad += sgv_pass_form_model(nullptr, sw, 3, 4, form, SGV_PF_N) == SGV_OK;
+    bad += sgv_pass_form_model(sh, sw, 3, 4, form, 0) != SGV_OK;
+    sw[SGV_SW_FIN_FORM] = 2;
+    bad += sgv_pass_form_model(sh, sw, 3, 4, form, SGV_PF_N) == SGV_OK;
   }
   std::printf(bad ? "FAILED %d\n" : "ok\n", bad);
   return bad ? 1 : 0;
