@@ -39,8 +39,8 @@ extern "C" {
 /* ABI revision of this header.  2: sgv_timers / sgv_exchange_stats take the
  * caller's buffer length (cap), sgv_comm_info added.  An integrator checks
  * sgv_abi_version() == SGV_ABI_VERSION before binding the rest.  Entry points
- * added since (sgv_posterior, the sgv_geno_* family, sgv_ld_pass_form and
- * sgv_pass_form_model) change no existing signature or layout and leave the
+ * added since (sgv_posterior, the sgv_geno_* family with its _reach entries,
+ * sgv_ld_pass_form and sgv_pass_form_model) change no existing signature or layout and leave the
  * revision at 2. */
 #define SGV_ABI_VERSION 2
 int sgv_abi_version(void);
@@ -322,6 +322,55 @@ int sgv_geno_clear(sgv_ctx* ctx);
 int sgv_geno_ld_band(sgv_ctx* ctx, int ld, int blk_local, int64_t window);
 int sgv_geno_coupling(sgv_ctx* ctx, int ld, int gb, int nr, int nc, const uint8_t* rows,
                       int64_t row_bytes, int nsamp, int64_t window, int64_t* counts_out);
+
+/* ---- distance-windowed genotype LD: a reach per row, a PSD-preserving taper --
+ * Positions.  Inside one LD block, in the run's marker order, marker i has a
+ * position pos[i] (f64): a base-pair coordinate (span D = 1000 x kb), a genetic
+ * position in cM (D = the cM), or, for a marker window with a taper, its index in
+ * the block (D = W + 1).  Positions are finite and non-decreasing inside a block;
+ * ties are allowed.
+ * Reach.  hi[i] = max{ j : i <= j < n_b, pos[j] - pos[i] <= D }, the predicate
+ * evaluated as that f64 subtraction and comparison (a searchsorted on pos + D is a
+ * first guess only, fixed up by testing the predicate at hi and hi + 1).  With a
+ * marker window W as well, hi[i] = min(hi[i], i + W): both limits apply, as in
+ * PLINK.  hi is non-decreasing and hi[i] >= i.
+ * Kept entries.  For j >= i, entry (i, j) is kept iff j <= hi[i]; everything else
+ * is exactly 0.0; the lower triangle is the mirror.
+ * Values.  Without a taper a kept entry is (G_b G_b^T)[i][j], sgv_geno_ld's
+ * sample-sequential fma chain, bit for bit.  With the triangular (Bartlett) taper
+ * it is acc * w, w = 1.0 - (pos[j] - pos[i]) / D, formed in exactly that order in
+ * f64 (one subtraction, one IEEE division, one subtraction, one multiplication; no
+ * contraction), rounded once to f32 on store when the context's precision is 32.
+ * w >= 0 follows from the reach predicate; the diagonal has w = 1, so R_ii =
+ * n_obs_i / nsamp as before; an entry at distance exactly D is stored as an
+ * explicit 0.0.  w(d) = max(0, 1 - d / D) is a positive-definite function on the
+ * line, so by the Schur product theorem R o [w(pos_i - pos_j)] is positive
+ * semi-definite whenever R = G G^T is, which a hard window is not.
+ * One window per taper: a taper needs exactly one of the three windows (its
+ * distance would be ambiguous with two).
+ * Storage.  With bw = max_i (hi[i] - i), sgv_set_ld_block_csr's rule: a packed
+ * band of panel extent round_up(256 + bw, 256), the packed triangle where that is
+ * >= n_b -- per block, so per band piece: the extent follows the widest reach in
+ * the piece.
+ *
+ * sgv_geno_ld_band_reach: block blk_local from the rows staged by
+ * sgv_geno_set_block, with the reach hi (n_b) and, for a taper, pos (n_b) and span
+ * D (pos NULL: no taper, span ignored).  State checks, storage and "stored block
+ * untouched on error" as sgv_geno_ld_band.  SGV_ERR_ARG: hi[i] outside [i, n_b -
+ * 1] or decreasing; with pos: a non-finite or decreasing position, span not finite
+ * or <= 0, or pos[hi[i]] - pos[i] > span (a negative weight).
+ * sgv_geno_coupling_reach: sgv_geno_coupling with keep (nr), a count of head
+ * columns per tail row: entry (a, c) is kept iff c < keep[a]; pos: the nr + nc
+ * halo rows' positions (NULL: no taper), the weight from pos[nr + c] - pos[a].  The
+ * same collective contract (rows, counts_out, keep and pos may be NULL where the
+ * rank owns neither piece).  SGV_ERR_ARG: keep[a] outside [0, nc] or decreasing,
+ * and the position errors above (pos[nr + keep[a] - 1] - pos[a] > span); an
+ * all-zero keep registers a zero coupling. */
+int sgv_geno_ld_band_reach(sgv_ctx* ctx, int ld, int blk_local, const int32_t* hi,
+                           const double* pos, double span);
+int sgv_geno_coupling_reach(sgv_ctx* ctx, int ld, int gb, int nr, int nc, const uint8_t* rows,
+                            int64_t row_bytes, int nsamp, const int32_t* keep, const double* pos,
+                            double span, int64_t* counts_out);
 
 /* ---- Hutchinson probes (host only, no device) ----------------------------
  * src/sgvamp.py:326 u = np.random.binomial(p=1/2, n=1, size=n)*2-1 from a legacy

@@ -899,6 +899,199 @@ extern "C" int sgv_geno_coupling(sgv_ctx* c, int ld, int gb, int nr, int nc, con
                          static_cast<const double*>(c->h_stage));
 }
 
+// ---------------------------------------------------------------------------
+// distance-windowed genotype LD: a reach per row, an optional triangular taper
+// ---------------------------------------------------------------------------
+// pos (n doubles, or NULL) and span of a taper: finite non-decreasing positions, a
+// finite span > 0; nullptr when they are usable, else what is wrong
+static const char* reach_pos_error(const double* pos, int64_t n, double span, int64_t* at) {
+  *at = -1;
+  if (!pos) return nullptr;
+  if (!std::isfinite(span) || span <= 0.0) return "the span is not a finite number > 0";
+  for (int64_t i = 0; i < n; ++i) {
+    *at = i;
+    if (!std::isfinite(pos[i])) return "a position is not finite";
+    if (i && pos[i] < pos[i - 1]) return "the positions decrease";
+  }
+  *at = -1;
+  return nullptr;
+}
+
+// reach (n int32) and, with a taper, positions (npos doubles) in one device
+// allocation, through the pinned staging buffer (sized by the caller)
+struct ReachAux {
+  void* d = nullptr;
+  const int32_t* d_reach = nullptr;
+  const double* d_pos = nullptr;
+  ~ReachAux() {
+    if (d) (void)hipFree(d);
+  }
+};
+static size_t reach_aux_bytes(int64_t n, int64_t npos, bool taper) {
+  return (size_t)round_up(4 * n, 8) + (taper ? sizeof(double) * (size_t)npos : 0);
+}
+static int reach_aux_upload(sgv_ctx* c, ReachAux& x, const int32_t* reach, int64_t n,
+                            const double* pos, int64_t npos) {
+  const size_t o = (size_t)round_up(4 * n, 8), bytes = reach_aux_bytes(n, npos, pos != nullptr);
+  HIPCHK(hipMalloc(&x.d, bytes));
+  uint8_t* hs = static_cast<uint8_t*>(c->h_stage);
+  std::memset(hs, 0, o);
+  std::memcpy(hs, reach, sizeof(int32_t) * (size_t)n);
+  if (pos) std::memcpy(hs + o, pos, sizeof(double) * (size_t)npos);
+  HIPCHK(hipMemcpyAsync(x.d, hs, bytes, hipMemcpyHostToDevice, c->st));
+  CHK(stream_wait(c));   // the staging buffer is free again
+  x.d_reach = static_cast<const int32_t*>(x.d);
+  if (pos) x.d_pos = reinterpret_cast<const double*>(static_cast<const uint8_t*>(x.d) + o);
+  return SGV_OK;
+}
+
+// R_b with a reach per row: sgv_geno_ld_band's storage rule at bw = max (hi[i] - i),
+// zeroed, then the kept entries from the bits
+extern "C" int sgv_geno_ld_band_reach(sgv_ctx* c, int ld, int b, const int32_t* hi,
+                                      const double* pos, double span) {
+  ENTER(c);
+  if (ld < 0 || ld >= c->nld || b < 0 || b >= c->nblk || !hi)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band_reach: bad arguments (ld %d, block %d)", ld, b);
+  const int64_t n = c->bn[b];
+  int64_t bw = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (hi[i] < i || hi[i] > n - 1 || (i && hi[i] < hi[i - 1]))
+      return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band_reach: reach hi[%lld] = %d of block %d (must "
+                  "be in [%lld, %lld] and non-decreasing)", (long long)i, (int)hi[i], b,
+                  (long long)i, (long long)n - 1);
+    bw = std::max<int64_t>(bw, hi[i] - i);
+  }
+  int64_t at;
+  if (const char* why = reach_pos_error(pos, n, span, &at))
+    return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band_reach: block %d: %s (span %g, marker %lld)", b,
+                why, span, (long long)at);
+  if (pos)
+    for (int64_t i = 0; i < n; ++i)
+      if (pos[hi[i]] - pos[i] > span)
+        return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band_reach: block %d: the reach of marker %lld "
+                    "(to %d) is farther than the span %g: the taper's weight would be negative", b,
+                    (long long)i, (int)hi[i], span);
+  if (!c->packing)
+    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band_reach: a band is a packed layout and packing "
+                "is off (sgv_set_ld_packing)");
+  if ((int)c->geno.size() != c->nblk || !c->geno[b].d_bits)
+    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band_reach: block %d has no genotypes "
+                "(sgv_geno_set_block)", b);
+  const GenoBlock& gb = c->geno[b];
+  if (gb.nbad)   // before any storage changes: the block stays as it was
+    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band_reach: block %d has %lld marker(s) without LD "
+                "(monomorphic or unobserved)", b, (long long)gb.nbad);
+  if (n > (int64_t)65535 * 64)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band_reach: block %d has %lld markers, at most %lld "
+                "are formed in one piece", b, (long long)n, (long long)65535 * 64);
+  ReachAux aux;
+  CHK(ensure_hstage(c, reach_aux_bytes(n, n, pos != nullptr)));
+  CHK(reach_aux_upload(c, aux, hi, n, pos, n));
+  int64_t ext = round_up(SYM_H + bw, BAND_Q);
+  if (ext >= n) ext = 0;   // the band is as wide as the triangle
+  CHK(ld_alloc(c, ld, b, 1, ext));
+  const LdBlock& lb = c->ldb[ld][b];
+  // a block kept from an earlier call of the same shape may hold a wider reach
+  const int64_t g1 = (int64_t)lb.poff.size() - 1;
+  const size_t elems = (size_t)(lb.poff[g1] + (n - g1 * SYM_H) * lb.pw[g1]);
+  HIPCHK(hipMemsetAsync(lb.ptr, 0, lb.esz() * elems, c->st));
+  HIPCHK(launch_bed_syrk_reach(gb.d_bits, gb.stride_w, gb.d_lut, (int)n, gb.nsamp, hi, aux.d_reach,
+                               aux.d_pos, span, ext, lb.ptr, lb.d_poff, lb.d_pw, lb.bits, c->st));
+  CHK(stream_wait(c));
+  std::fill(c->rx0_valid.begin(), c->rx0_valid.end(), 0);
+  return SGV_OK;
+}
+
+// sgv_geno_coupling with a count of kept head columns per tail row
+extern "C" int sgv_geno_coupling_reach(sgv_ctx* c, int ld, int gb, int nr, int nc,
+                                       const uint8_t* rows, int64_t row_bytes, int nsamp,
+                                       const int32_t* keep, const double* pos, double span,
+                                       int64_t* counts_out) {
+  ENTER(c);
+  if (ld < 0 || ld >= c->nld || gb < 0 || gb + 1 >= c->nblk_global || nr < 1 || nc < 1)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: bad arguments (ld %d, gb %d, %d x %d)",
+                ld, gb, nr, nc);
+  const int ba = gb - c->blk0, bb = gb + 1 - c->blk0;
+  const bool own = (ba >= 0 && ba < c->nblk) || (bb >= 0 && bb < c->nblk);
+  if (!own) return ld_set_coupling(c, "sgv_geno_coupling_reach", ld, gb, nr, nc, nullptr);
+  if (!rows || !counts_out || !keep || nsamp < 1 || row_bytes < ((int64_t)nsamp + 3) / 4)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: bad rows (coupling %d, %d samples, rows "
+                "of %lld bytes)", gb, nsamp, (long long)row_bytes);
+  if ((ba >= 0 && ba < c->nblk && nr > c->bn[ba]) || (bb >= 0 && bb < c->nblk && nc > c->bn[bb]))
+    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: %d x %d exceeds the pieces", nr, nc);
+  const int64_t n = (int64_t)nr + nc;
+  int kmax = 0;
+  for (int a = 0; a < nr; ++a) {
+    if (keep[a] < 0 || keep[a] > nc || (a && keep[a] < keep[a - 1]))
+      return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: keep[%d] = %d of coupling %d (must be "
+                  "in [0, %d] and non-decreasing)", a, (int)keep[a], gb, nc);
+    kmax = std::max<int>(kmax, keep[a]);
+  }
+  int64_t at;
+  if (const char* why = reach_pos_error(pos, n, span, &at))
+    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: coupling %d: %s (span %g, halo row "
+                "%lld)", gb, why, span, (long long)at);
+  if (pos)
+    for (int a = 0; a < nr; ++a)
+      if (keep[a] > 0 && pos[nr + keep[a] - 1] - pos[a] > span)
+        return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: coupling %d: tail row %d keeps %d "
+                    "head column(s), farther than the span %g: the taper's weight would be "
+                    "negative", gb, a, (int)keep[a], span);
+  const int64_t used = ((int64_t)nsamp + 3) / 4;
+  const int64_t stride_w = ((int64_t)nsamp + 15) / 16;
+  const size_t bits_bytes = (size_t)n * stride_w * 4;
+  const size_t cnt_bytes = sizeof(long long) * 4 * (size_t)n;
+  const size_t c_bytes = sizeof(double) * (size_t)nr * nc;
+  GenoBlock h;       // the halo's rows and tables, freed on every way out
+  struct Guard {
+    GenoBlock& g;
+    double* d_C = nullptr;
+    ~Guard() {
+      geno_free(g);
+      if (d_C) (void)hipFree(d_C);
+    }
+  } guard{h};
+  ReachAux aux;
+  HIPCHK(hipMalloc(&h.d_bits, bits_bytes));
+  HIPCHK(hipMalloc(&h.d_lut, sizeof(double) * 4 * n));
+  HIPCHK(hipMalloc(&h.d_msd, sizeof(double) * 2 * n));
+  HIPCHK(hipMalloc(&guard.d_C, c_bytes));
+  CHK(ensure_hstage(c, std::max(std::max(std::max(bits_bytes, cnt_bytes), c_bytes),
+                                reach_aux_bytes(nr, n, pos != nullptr))));
+  CHK(ensure_stage(c, cnt_bytes));
+  uint8_t* hs = static_cast<uint8_t*>(c->h_stage);
+  std::memset(hs, 0, bits_bytes);
+  for (int64_t i = 0; i < n; ++i)
+    std::memcpy(hs + (size_t)i * stride_w * 4, rows + (size_t)i * row_bytes, (size_t)used);
+  HIPCHK(hipMemcpyAsync(h.d_bits, hs, bits_bytes, hipMemcpyHostToDevice, c->st));
+  long long* d_cnt = static_cast<long long*>(c->d_stage);
+  HIPCHK(launch_bed_stats(h.d_bits, stride_w, (int)n, nsamp, d_cnt, h.d_lut, h.d_msd, c->st));
+  CHK(stream_wait(c));   // the bits have left the staging buffer
+  HIPCHK(hipMemcpyAsync(c->h_stage, d_cnt, cnt_bytes, hipMemcpyDeviceToHost, c->st));
+  CHK(stream_wait(c));
+  const long long* hc = static_cast<const long long*>(c->h_stage);
+  int64_t nbad = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const long long c0 = hc[4 * i], c2 = hc[4 * i + 2], c3 = hc[4 * i + 3];
+    const long long nobs = c0 + c2 + c3, S1 = 2 * c0 + c2, S2 = 4 * c0 + c2;
+    if (nobs == 0 || nobs * S2 - S1 * S1 == 0) ++nbad;
+    for (int k = 0; k < 4; ++k) counts_out[4 * i + k] = (int64_t)hc[4 * i + k];
+  }
+  if (nbad)   // nothing registered: the coupling stays as it was
+    return fail(c, SGV_ERR_STATE, "sgv_geno_coupling_reach: coupling %d has %lld marker(s) "
+                "without LD (monomorphic or unobserved)", gb, (long long)nbad);
+  HIPCHK(hipMemsetAsync(guard.d_C, 0, c_bytes, c->st));
+  if (kmax > 0) {   // an all-zero keep: the zero coupling
+    CHK(reach_aux_upload(c, aux, keep, nr, pos, n));
+    HIPCHK(launch_bed_cross_reach(h.d_bits, stride_w, h.d_lut, nr, nc, nsamp, aux.d_reach, kmax,
+                                  aux.d_pos, span, c->ld_bits, guard.d_C, c->st));
+  }
+  HIPCHK(hipMemcpyAsync(c->h_stage, guard.d_C, c_bytes, hipMemcpyDeviceToHost, c->st));
+  CHK(stream_wait(c));
+  return ld_set_coupling(c, "sgv_geno_coupling_reach", ld, gb, nr, nc,
+                         static_cast<const double*>(c->h_stage));
+}
+
 extern "C" int sgv_geno_r(sgv_ctx* c, int k, const double* y) {
   ENTER(c);
   if (k < 0 || k >= c->K || !y) return fail(c, SGV_ERR_ARG, "sgv_geno_r: bad arguments");

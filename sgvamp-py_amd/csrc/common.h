@@ -735,6 +735,20 @@ hipError_t launch_bed_syrk_band(const uint32_t* d_bits, int64_t stride_w, const 
 hipError_t launch_bed_cross(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int nr,
                             int nc, int nsamp, int64_t window, int bits, double* d_C,
                             hipStream_t st);
+// distance-windowed R: entries (i, j), i <= j <= hi[i] (hi: the host's copy of d_hi,
+// checked by the caller, sizes the grid), times 1 - (pos[j] - pos[i]) / span where
+// d_pos is given; storage, zeroing and rounding as launch_bed_syrk_band's
+hipError_t launch_bed_syrk_reach(const uint32_t* d_bits, int64_t stride_w, const double* d_lut,
+                                 int n, int nsamp, const int32_t* hi, const int32_t* d_hi,
+                                 const double* d_pos, double span, int64_t ext, void* d_R,
+                                 const int64_t* d_poff, const int64_t* d_pw, int bits,
+                                 hipStream_t st);
+// launch_bed_cross with entries (a, c), c < keep[a] (kmax: the largest, >= 1), times
+// 1 - (pos[nr + c] - pos[a]) / span where d_pos (nr + nc positions) is given
+hipError_t launch_bed_cross_reach(const uint32_t* d_bits, int64_t stride_w, const double* d_lut,
+                                  int nr, int nc, int nsamp, const int32_t* d_keep, int kmax,
+                                  const double* d_pos, double span, int bits, double* d_C,
+                                  hipStream_t st);
 hipError_t launch_bed_row_dot(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int n,
                               int nsamp, const double* d_y, double* d_out, hipStream_t st);
 hipError_t launch_bed_g_accum(const uint32_t* d_bits, int64_t stride_w, const double* d_msd, int n,

@@ -345,6 +345,153 @@ hipError_t launch_bed_cross(const uint32_t* d_bits, int64_t stride_w, const doub
   return hipGetLastError();
 }
 
+// Distance-windowed R (include/sgvamp_hip.h, "distance-windowed genotype LD"):
+// k_bed_syrk_band's grid and contraction with a reach per row instead of one W.
+// Entry (i, j), j >= i, is stored iff j <= hi[i]; hi is non-decreasing, so row
+// min(i0 + 63, n - 1) has the tile's farthest reach and a tile past it returns
+// before loading.  TAPER: the finished sum times w = 1 - (pos[j] - pos[i]) / span,
+// formed in that order in f64 (one subtraction, one division, one subtraction,
+// one multiplication; w >= 0 by the reach predicate), rounded once on store.  The
+// mirror, the stored-extent guard and the caller's memset are k_bed_syrk_band's.
+template <class T, bool TAPER>
+__global__ __launch_bounds__(256) void k_bed_syrk_reach(const uint8_t* __restrict__ bits,
+                                                        int64_t stride_b,
+                                                        const double* __restrict__ lut, int n,
+                                                        int nsamp, const int32_t* __restrict__ hi,
+                                                        const double* __restrict__ pos,
+                                                        double span, int64_t ext,
+                                                        T* __restrict__ R,
+                                                        const int64_t* __restrict__ poff,
+                                                        const int64_t* __restrict__ pw) {
+  const int ti = blockIdx.y;
+  const int64_t tj = (int64_t)ti + blockIdx.x;
+  const int i0 = ti * 64;
+  // no column, or the first column is past the reach of the tile's last row: nothing to load
+  if (tj * 64 >= n || tj * 64 > hi[i0 + 63 < n ? i0 + 63 : n - 1]) return;
+  const int j0 = (int)tj * 64;
+  double acc[4][4];
+  bed_tile(bits, lut, i0, n, bits, lut, j0, n, stride_b, nsamp, acc);
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int i = i0 + ty + 16 * a;
+    if (i >= n) continue;
+    const int hi_i = hi[i];
+    const int r0 = i / SYM_H * SYM_H;
+    const int64_t cols = ext > 0 && ext < n - r0 ? ext : n - r0;   // the panel's stored columns
+    double pi = 0.0;
+    if (TAPER) pi = pos[i];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int j = j0 + tx + 16 * b;
+      if (j >= n || j < i || j > hi_i) continue;
+      if (j - r0 >= cols) continue;        // cannot happen: j <= hi[i] <= i + bw < r0 + 256 + bw <= r0 + ext
+      double v = acc[a][b];
+      if (TAPER) {
+        const double w = 1.0 - (pos[j] - pi) / span;
+        v = v * w;
+      }
+      *sym_addr(R, poff, pw, i, j) = (T)v;
+      if (j != i && j < r0 + SYM_H) *sym_addr(R, poff, pw, j, i) = (T)v;
+    }
+  }
+}
+
+// hi: the host's copy of d_hi (checked by the caller: i <= hi[i] <= n - 1, non-
+// decreasing), from which the grid's width is the most column tiles any row tile
+// reaches -- never the square of tiles unless the reach is the triangle
+hipError_t launch_bed_syrk_reach(const uint32_t* d_bits, int64_t stride_w, const double* d_lut,
+                                 int n, int nsamp, const int32_t* hi, const int32_t* d_hi,
+                                 const double* d_pos, double span, int64_t ext, void* d_R,
+                                 const int64_t* d_poff, const int64_t* d_pw, int bits,
+                                 hipStream_t st) {
+  const int64_t nt = ((int64_t)n + 63) / 64;
+  if (n < 1 || nt > 65535 || !hi || !d_hi) return hipErrorInvalidValue;
+  int64_t nx = 1;
+  for (int64_t ti = 0; ti < nt; ++ti)
+    nx = std::max<int64_t>(nx, hi[std::min<int64_t>(64 * ti + 63, n - 1)] / 64 - ti + 1);
+  const dim3 grid((unsigned)nx, (unsigned)nt);
+  const uint8_t* by = reinterpret_cast<const uint8_t*>(d_bits);
+  if (bits == 32) {
+    if (d_pos)
+      hipLaunchKernelGGL((k_bed_syrk_reach<float, true>), grid, dim3(256), 0, st, by, stride_w * 4,
+                         d_lut, n, nsamp, d_hi, d_pos, span, ext, (float*)d_R, d_poff, d_pw);
+    else
+      hipLaunchKernelGGL((k_bed_syrk_reach<float, false>), grid, dim3(256), 0, st, by,
+                         stride_w * 4, d_lut, n, nsamp, d_hi, d_pos, span, ext, (float*)d_R, d_poff,
+                         d_pw);
+  } else {
+    if (d_pos)
+      hipLaunchKernelGGL((k_bed_syrk_reach<double, true>), grid, dim3(256), 0, st, by,
+                         stride_w * 4, d_lut, n, nsamp, d_hi, d_pos, span, ext, (double*)d_R,
+                         d_poff, d_pw);
+    else
+      hipLaunchKernelGGL((k_bed_syrk_reach<double, false>), grid, dim3(256), 0, st, by,
+                         stride_w * 4, d_lut, n, nsamp, d_hi, d_pos, span, ext, (double*)d_R,
+                         d_poff, d_pw);
+  }
+  return hipGetLastError();
+}
+
+// k_bed_cross with a count of kept head columns per tail row: entry (a, c) is
+// stored iff c < keep[a]; keep is non-decreasing, so row min(a0 + 63, nr - 1) has
+// the tile's largest count.  TAPER: times w = 1 - (pos[nr + c] - pos[a]) / span
+// (pos: the nr + nc halo rows' positions), as k_bed_syrk_reach forms it.
+template <bool TAPER>
+__global__ __launch_bounds__(256) void k_bed_cross_reach(const uint8_t* __restrict__ bits,
+                                                         int64_t stride_b,
+                                                         const double* __restrict__ lut, int nr,
+                                                         int nc, int nsamp,
+                                                         const int32_t* __restrict__ keep,
+                                                         const double* __restrict__ pos,
+                                                         double span, int f32,
+                                                         double* __restrict__ C) {
+  const int a0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+  if (a0 >= nr || c0 >= nc || c0 >= keep[a0 + 63 < nr ? a0 + 63 : nr - 1]) return;
+  double acc[4][4];
+  bed_tile(bits, lut, a0, nr, bits + (int64_t)nr * stride_b, lut + 4 * (int64_t)nr, c0, nc,
+           stride_b, nsamp, acc);
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int ia = a0 + ty + 16 * a;
+    if (ia >= nr) continue;
+    const int k = keep[ia];
+    double pa = 0.0;
+    if (TAPER) pa = pos[ia];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int ic = c0 + tx + 16 * b;
+      if (ic >= nc || ic >= k) continue;
+      double v = acc[a][b];
+      if (TAPER) {
+        const double w = 1.0 - (pos[nr + ic] - pa) / span;
+        v = v * w;
+      }
+      C[(int64_t)ia * nc + ic] = f32 ? (double)(float)v : v;
+    }
+  }
+}
+
+// kmax: the largest keep (the caller's, from its host copy): the grid covers the
+// kept columns only
+hipError_t launch_bed_cross_reach(const uint32_t* d_bits, int64_t stride_w, const double* d_lut,
+                                  int nr, int nc, int nsamp, const int32_t* d_keep, int kmax,
+                                  const double* d_pos, double span, int bits, double* d_C,
+                                  hipStream_t st) {
+  if (nr < 1 || nc < 1 || kmax < 1 || kmax > nc || !d_keep || (nr + 63) / 64 > 65535)
+    return hipErrorInvalidValue;
+  const dim3 grid((kmax + 63) / 64, (nr + 63) / 64);
+  const uint8_t* by = reinterpret_cast<const uint8_t*>(d_bits);
+  if (d_pos)
+    hipLaunchKernelGGL(k_bed_cross_reach<true>, grid, dim3(256), 0, st, by, stride_w * 4, d_lut,
+                       nr, nc, nsamp, d_keep, d_pos, span, bits == 32 ? 1 : 0, d_C);
+  else
+    hipLaunchKernelGGL(k_bed_cross_reach<false>, grid, dim3(256), 0, st, by, stride_w * 4, d_lut,
+                       nr, nc, nsamp, d_keep, d_pos, span, bits == 32 ? 1 : 0, d_C);
+  return hipGetLastError();
+}
+
 // out[i] = sum_n t_i[code_in] y[n]; one wave per marker, k_row_dot's lane order
 __global__ __launch_bounds__(256) void k_bed_row_dot(const uint8_t* __restrict__ bits,
                                                      int64_t stride_b,

@@ -282,6 +282,61 @@ class Engine:
         self.ctx.check(rc, "sgv_geno_coupling")
         return counts
 
+    def geno_ld_band_reach(self, ld, b_global, hi, pos=None, span=0.0):
+        """Distance-windowed R_b of the staged genotypes (include/sgvamp_hip.h,
+        "distance-windowed genotype LD"): entries (i, j), i <= j <= hi[i], mirrored,
+        0 elsewhere; with pos (the block's positions) and span each times 1 -
+        (pos[j] - pos[i]) / span, the triangular taper.  A packed band by the widest
+        reach (this rank's block; the engine's precision; packing must be on)."""
+        if not (self.b0 <= b_global < self.b1):
+            return
+        hi = np.ascontiguousarray(hi, dtype=np.int32).ravel()
+        n = int(self.block_sizes[b_global])
+        if len(hi) != n or (pos is not None and np.size(pos) != n):
+            raise ValueError("reach of block %d: %d entries (positions: %s), the block has %d "
+                             "markers" % (b_global, len(hi),
+                                          "none" if pos is None else np.size(pos), n))
+        pp = None
+        if pos is not None:
+            pos = np.ascontiguousarray(pos, dtype=np.float64).ravel()
+            pp = hb.dptr(pos)
+        self.ctx.sgv_geno_ld_band_reach(int(ld), b_global - self.b0,
+                                        hi.ctypes.data_as(hb._c_i32_p), pp, float(span))
+
+    def geno_coupling_reach(self, ld, gb, nr, nc, rows, nsamp, keep, pos=None, span=0.0,
+                            check=None):
+        """geno_coupling with keep (nr counts of head columns: entry (a, c) is kept
+        iff c < keep[a]) in place of the window and, for the taper, pos (the nr + nc
+        halo rows' positions) and span.  Called on every rank for every coupling."""
+        own = self.b0 <= gb < self.b1 or self.b0 <= gb + 1 < self.b1
+        n = int(nr) + int(nc)
+        counts, rp, cp, kp, pp, nb = None, None, None, None, None, 0
+        if own:
+            rows = np.asarray(rows() if callable(rows) else rows)
+            if rows.dtype != np.uint8 or rows.ndim != 2 or rows.shape[0] != n \
+                    or rows.shape[1] < (int(nsamp) + 3) // 4 or int(nsamp) < 1:
+                raise ValueError("genotype rows of coupling %d: %s %s, expected uint8 (%d, >= %d)"
+                                 % (gb, rows.dtype, rows.shape, n, (int(nsamp) + 3) // 4))
+            rows = np.ascontiguousarray(rows)
+            keep = np.ascontiguousarray(keep, dtype=np.int32).ravel()
+            if len(keep) != int(nr) or (pos is not None and np.size(pos) != n):
+                raise ValueError("coupling %d: %d kept-column counts for %d tail rows (positions: "
+                                 "%s for %d halo rows)" % (gb, len(keep), int(nr),
+                                                           "none" if pos is None else np.size(pos), n))
+            counts = np.zeros((n, 4), dtype=np.int64)
+            rp, cp, nb = rows.ctypes.data_as(hb._c_u8_p), counts.ctypes.data_as(hb._c_i64_p), \
+                int(rows.shape[1])
+            kp = keep.ctypes.data_as(hb._c_i32_p)
+            if pos is not None:
+                pos = np.ascontiguousarray(pos, dtype=np.float64).ravel()
+                pp = hb.dptr(pos)
+        rc = self.ctx.lib.sgv_geno_coupling_reach(self.ctx.h, int(ld), int(gb), int(nr), int(nc),
+                                                  rp, nb, int(nsamp), kp, pp, float(span), cp)
+        if rc != hb.SGV_OK and check is not None and counts is not None:
+            check(counts)
+        self.ctx.check(rc, "sgv_geno_coupling_reach")
+        return counts
+
     def geno_r(self, k, y):
         """r_k = G y over this rank's blocks (get_vector(VEC_R, k) reads it)."""
         y = np.ascontiguousarray(y, dtype=np.float64).ravel()

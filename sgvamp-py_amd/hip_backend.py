@@ -41,6 +41,7 @@ PassForm = collections.namedtuple("PassForm", PASS_FORM_FIELDS)
 
 _c_int_p = ctypes.POINTER(ctypes.c_int)
 _c_i64_p = ctypes.POINTER(ctypes.c_int64)
+_c_i32_p = ctypes.POINTER(ctypes.c_int32)
 _c_dbl_p = ctypes.POINTER(ctypes.c_double)
 _c_i8_p = ctypes.POINTER(ctypes.c_int8)
 _c_u8_p = ctypes.POINTER(ctypes.c_uint8)
@@ -90,6 +91,11 @@ _SIGS = {
     "sgv_geno_ld_band": [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64],
     "sgv_geno_coupling": [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_u8_p,
                           ctypes.c_int64, ctypes.c_int, ctypes.c_int64, _c_i64_p],
+    "sgv_geno_ld_band_reach": [_vp, ctypes.c_int, ctypes.c_int, _c_i32_p, _c_dbl_p,
+                               ctypes.c_double],
+    "sgv_geno_coupling_reach": [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                _c_u8_p, ctypes.c_int64, ctypes.c_int, _c_i32_p, _c_dbl_p,
+                                ctypes.c_double, _c_i64_p],
     "sgv_geno_r": [_vp, ctypes.c_int, _c_dbl_p],
     "sgv_geno_g": [_vp, _c_dbl_p, _c_dbl_p],
     "sgv_geno_clear": [_vp],

@@ -15,7 +15,9 @@
 * genotypes:  a PLINK 1 .bed/.bim/.fam panel (read_bed) as an LD source: BedLD
               forms each LD block on the device from the block's 2-bit rows
               (simulation/sim_phen.py:33-37 reads such a panel with bed_reader;
-              here NumPy only)
+              here NumPy only); windowed by markers, by the .bim's kb or cM, with
+              an optional triangular taper; one block per chromosome
+              (chromosome_blocks)
 """
 import json
 import os
@@ -195,15 +197,42 @@ def _bed_prefix(path):
 class BedPanel:
     """A PLINK 1 .bed/.bim/.fam panel: ``rows`` is a read-only memmap (M,
     ceil(N / 4)) of the SNP-major 2-bit codes, ``N`` the .fam sample count,
-    ``ids`` the .bim variant ids (row order)."""
+    ``ids`` the .bim variant ids (row order).  ``chrom``, ``cm``, ``bp``: the
+    .bim's chromosome, genetic-position and base-pair columns as written (row
+    order; None where the panel was made without them), read as numbers only by
+    positions()."""
 
-    def __init__(self, prefix, rows, N, ids):
+    def __init__(self, prefix, rows, N, ids, chrom=None, cm=None, bp=None):
         self.prefix, self.rows, self.N, self.ids = prefix, rows, int(N), list(ids)
+        self.chrom, self.cm, self.bp = (None if c is None else list(c) for c in (chrom, cm, bp))
+        for name, col in (("chrom", self.chrom), ("cm", self.cm), ("bp", self.bp)):
+            if col is not None and len(col) != len(self.ids):
+                raise ValueError("%d %s entries for %d variants" % (len(col), name, len(self.ids)))
         self._index = None
 
     @property
     def M(self):
         return len(self.ids)
+
+    def positions(self, unit, select=None):
+        """The ``bp`` or ``cm`` column of the given panel rows (default: all) as
+        f64; a value that is not a finite number is a ValueError naming its variant."""
+        col = {"bp": self.bp, "cm": self.cm}[unit]
+        name = {"bp": "base-pair", "cm": "cM"}[unit]
+        if col is None:
+            raise ValueError("the panel %s carries no %s positions" % (self.prefix, name))
+        rows = range(len(col)) if select is None else [int(i) for i in select]
+        out = np.empty(len(rows), dtype=np.float64)
+        for k, i in enumerate(rows):
+            try:
+                out[k] = float(col[i])
+                ok = np.isfinite(out[k])
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("%s.bim: the %s position %r of variant %s is not a number"
+                                 % (self.prefix, name, col[i], self.ids[i]))
+        return out
 
     def index_of(self, variants):
         """Panel rows of the given variant ids, in their order; a variant the
@@ -227,7 +256,11 @@ def read_bed(prefix):
     with open(prefix + ".fam") as f:
         N = sum(1 for line in f if line.strip())
     with open(prefix + ".bim") as f:
-        ids = [line.split()[1] for line in f if line.strip()]
+        bim = [line.split() for line in f if line.strip()]
+    ids = [t[1] for t in bim]
+    # chromosome, id, cM, bp: kept as written (a .bim of fewer columns has none)
+    chrom, cm, bp = ([t[c] for t in bim] if all(len(t) > c for t in bim) else None
+                     for c in (0, 2, 3))
     bed = prefix + ".bed"
     with open(bed, "rb") as f:
         head = f.read(3)
@@ -246,7 +279,7 @@ def read_bed(prefix):
                          "samples of its .fam" % (bed, size, M, nb, 3 + M * nb, N))
     rows = np.memmap(bed, dtype=np.uint8, mode="r", offset=3, shape=(M, nb)) if M else \
         np.zeros((0, nb), dtype=np.uint8)
-    return BedPanel(prefix, rows, N, ids)
+    return BedPanel(prefix, rows, N, ids, chrom=chrom, cm=cm, bp=bp)
 
 
 def write_bed(prefix, codes, bim_rows, fam_rows):
@@ -312,11 +345,25 @@ class BedLD(BlockLD):
     pieces, and pieces() gives those pieces' couplings as GenoCoupling objects,
     formed on the device from the 2 * window rows next to each cut.  Truncating
     LD to a window does not preserve positive semi-definiteness; the ridge ``s``
-    is the remedy."""
+    is the remedy -- or ``taper``.
+
+    ``window_kb`` / ``window_cm`` (positive floats): a window by distance, the
+    .bim's base-pair column with span D = 1000 window_kb, or its cM column with D =
+    window_cm (include/sgvamp_hip.h, "distance-windowed genotype LD").  Marker i
+    then reaches hi[i] = max{j >= i : pos[j] - pos[i] <= D} (reach(b), from the
+    .bim alone), cut to i + window where ``window`` is given as well; entry (i, j),
+    j >= i, is kept iff j <= hi[i].  Positions must not decrease inside a block.
+    ``taper`` = "triangle" multiplies every kept entry by 1 - (pos[j] - pos[i]) /
+    D, which keeps the windowed block positive semi-definite (the Schur product
+    with a positive-definite function), so it needs no ridge.  A taper needs
+    exactly one of the three windows; with ``window`` alone the positions are the
+    markers' indices in the block and D = window + 1.  The band's width is the
+    widest reach, max(hi - i), per block and per piece."""
 
     uses_geno = True
 
-    def __init__(self, panel, block_sizes, select=None, s=0.0, window=None):
+    def __init__(self, panel, block_sizes, select=None, s=0.0, window=None, window_kb=None,
+                 window_cm=None, taper=None, _pos=None):
         sizes = [int(b) for b in block_sizes]
         super().__init__(block_sizes=sizes, loader=self._host_block, s=s)
         self.panel = panel
@@ -327,6 +374,82 @@ class BedLD(BlockLD):
                              % (sum(sizes), m))
         self._offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         self.window = check_ld_window(window)
+        self.window_kb = check_ld_distance(window_kb, "kb")
+        self.window_cm = check_ld_distance(window_cm, "cM")
+        self.taper = check_ld_taper(taper)
+        given = sum(w is not None for w in (self.window, self.window_kb, self.window_cm))
+        if self.taper is not None and given != 1:
+            raise ValueError("an LD taper needs exactly one of the windows (markers, kb, cM) as "
+                             "its distance: %d given" % given)
+        if self.window_kb is not None and self.window_cm is not None:
+            raise ValueError("an LD window in kb and one in cM exclude each other")
+        # a reach per row (distance window and / or taper); a marker window alone
+        # stays on the uniform-window path
+        self.by_reach = any(x is not None for x in (self.taper, self.window_kb, self.window_cm))
+        self._pos, self._span, self._hi = None, None, {}
+        if self.by_reach:
+            self._set_positions(_pos)
+
+    def _set_positions(self, pos):
+        """Every selected marker's position and the span D; the checks of each
+        block's positions (a piece partition takes its parent's, checked there)."""
+        if self.window_kb is not None:
+            unit, self._span = "bp", 1000.0 * self.window_kb
+        elif self.window_cm is not None:
+            unit, self._span = "cm", self.window_cm
+        else:
+            unit, self._span = None, float(self.window + 1)
+        if pos is not None:
+            self._pos = pos
+            return
+        if unit is None:    # a tapered marker window: the index in the block
+            self._pos = np.concatenate([np.arange(n, dtype=np.float64) for n in self.block_sizes])
+            return
+        self._pos = self.panel.positions(unit, self.select)
+        name = {"bp": "base-pair", "cm": "cM"}[unit]
+        for b in range(len(self.block_sizes)):
+            p = self._pos[int(self._offs[b]):int(self._offs[b + 1])]
+            down = np.flatnonzero(np.diff(p) < 0)
+            if len(down):
+                ids, k = self.variant_ids(b), int(down[0])
+                raise ValueError("LD block %d: the %s positions decrease from %s (%s) to %s (%s); "
+                                 "a distance window needs them in order inside every block"
+                                 % (b, name, ids[k], repr(float(p[k])), ids[k + 1],
+                                    repr(float(p[k + 1]))))
+            if unit == "cm" and len(p) > 1 and p[0] == p[-1]:
+                raise ValueError("LD block %d: every marker has the cM position %s: %s.bim "
+                                 "carries no genetic map, so a window in cM keeps everything"
+                                 % (b, repr(float(p[0])), self.panel.prefix))
+
+    def positions(self, b):
+        """Block b's positions (by_reach only)."""
+        return self._pos[int(self._offs[b]):int(self._offs[b + 1])]
+
+    def reach(self, b):
+        """hi (n_b,) int32: hi[i] = max{j : i <= j < n_b, pos[j] - pos[i] <= D}, cut
+        to i + window where a marker window is given too.  The predicate is that
+        f64 subtraction and comparison: searchsorted on pos + D is a first guess,
+        fixed up by testing it at hi and hi + 1."""
+        if b not in self._hi:
+            p, D = self.positions(b), self._span
+            n = len(p)
+            i = np.arange(n)
+            hi = np.clip(np.searchsorted(p, p + D, side="right") - 1, i, n - 1)
+            while True:
+                far = (p[hi] - p[i] > D) & (hi > i)
+                if not far.any():
+                    break
+                hi = hi - far
+            while True:
+                nxt = np.minimum(hi + 1, n - 1)
+                near = (hi + 1 < n) & (p[nxt] - p[i] <= D)
+                if not near.any():
+                    break
+                hi = hi + near
+            if self.window is not None:
+                hi = np.minimum(hi, i + self.window)
+            self._hi[b] = hi.astype(np.int32)
+        return self._hi[b]
 
     def _index(self, b):
         o0, o1 = int(self._offs[b]), int(self._offs[b + 1])
@@ -383,6 +506,9 @@ class BedLD(BlockLD):
     def _host_block(self, b):
         G, _ = self.standardised(b)
         R = G @ G.T
+        if self.by_reach:
+            return reach_masked(R, self.reach(b), self.positions(b) if self.taper else None,
+                                self._span)
         if self.window is not None:
             i = np.arange(R.shape[0])
             R[np.abs(i[:, None] - i[None, :]) > self.window] = 0.0
@@ -392,15 +518,23 @@ class BedLD(BlockLD):
         return None
 
     def band_width(self, b):
-        """min(window, n_b - 1) of a windowed source; None (a dense block) without."""
+        """min(window, n_b - 1) of a windowed source, the widest reach max(hi - i) of
+        a distance-windowed one (from the .bim alone: no genotype is read); None (a
+        dense block) without a window."""
+        if self.by_reach:
+            hi = self.reach(b)
+            return int(np.max(hi - np.arange(len(hi))))
         return None if self.window is None else min(self.window, self.block_sizes[b] - 1)
 
     def symmetric(self, b, A=None):
-        return True if self.window is not None else super().symmetric(b, A)
+        return True if self.window is not None or self.by_reach else super().symmetric(b, A)
 
     def upload(self, eng, ld, b, packed=True):
         """Stage block b's rows on the engine and form R_b there (this rank's
         blocks only; `packed` is the engine's own setting)."""
+        if self.by_reach and not packed:
+            raise ValueError("distance-windowed genotype LD is stored as a packed band: it needs "
+                             "LD packing on")
         if self.window is not None and not packed:
             raise ValueError("windowed genotype LD (window %d) is stored as a packed band: "
                              "it needs LD packing on" % self.window)
@@ -408,7 +542,10 @@ class BedLD(BlockLD):
             return
         counts = eng.geno_set_block(b, self.rows(b), self.panel.N)
         self.check_counts(b, counts)
-        if self.window is not None:
+        if self.by_reach:
+            eng.geno_ld_band_reach(ld, b, self.reach(b),
+                                   self.positions(b) if self.taper else None, self._span)
+        elif self.window is not None:
             eng.geno_ld_band(ld, b, self.window)
         else:
             eng.geno_ld(ld, b)
@@ -423,21 +560,32 @@ class BedLD(BlockLD):
         sizes = [int(n) for ps in cuts for n in ps]
         if len(sizes) == len(self.block_sizes):
             return self, {}
-        if self.window is None:
+        if self.window is None and not self.by_reach:
             raise ValueError("a genotype LD source without a window has dense blocks: no pieces")
-        L = BedLD(self.panel, sizes, select=self.select, s=self.s, window=self.window)
+        # by reach: the pieces keep the original blocks' positions (a tapered marker
+        # window's are indices in the original block, so a cut changes no weight) and
+        # a piece's reach is the block's, cut at the piece's end
+        L = BedLD(self.panel, sizes, select=self.select, s=self.s, window=self.window,
+                  window_kb=self.window_kb, window_cm=self.window_cm, taper=self.taper,
+                  _pos=self._pos)
         couplings = {}
         k = 0
         for b, ps in enumerate(cuts):
             if len(ps) > 1:
                 bw = max(1, self.band_width(b))
-                o = int(self._offs[b])
+                b0 = o = int(self._offs[b])
                 for i in range(len(ps) - 1):
                     cut = o + int(ps[i])
                     nr, nc = min(bw, int(ps[i])), min(bw, int(ps[i + 1]))
                     m = np.arange(cut - nr, cut + nc)
+                    keep = pos = None
+                    if self.by_reach:   # head columns tail row a keeps: up to hi, from the cut on
+                        hi = self.reach(b).astype(np.int64) + b0
+                        keep = np.clip(hi[cut - nr - b0:cut - b0] - cut + 1, 0, nc)
+                        pos = self._pos[m] if self.taper else None
                     couplings[k + i] = GenoCoupling(
-                        L, nr, nc, m if self.select is None else self.select[m])
+                        L, nr, nc, m if self.select is None else self.select[m], keep=keep,
+                        pos=pos)
                     o = cut
             k += len(ps)
         return L, couplings
@@ -450,7 +598,7 @@ class BedLD(BlockLD):
         if list(sizes) == list(self.block_sizes):
             return self
         L = super().regroup(sizes)
-        if self.window is not None:
+        if self.window is not None or self.by_reach:
             from sgvamp import _dense_guard
 
             assemble = L._loader
@@ -467,14 +615,25 @@ class GenoCoupling:
     """Coupling between band pieces gb and gb + 1 of a windowed BedLD, kept as the
     panel rows of its halo: ``index`` = the panel rows of gb's last nr markers,
     then of gb + 1's first nc.  C = G_tail G_head^T masked to the window is formed
-    on the device (upload); host() is the same in NumPy, for checks."""
+    on the device (upload); host() is the same in NumPy, for checks.  Of a
+    distance-windowed BedLD: ``keep`` (nr,) = the head columns each tail row keeps
+    (entry (a, c) iff c < keep[a]) and, with a taper, ``pos`` = the halo rows'
+    positions (the weight of (a, c) is 1 - (pos[nr + c] - pos[a]) / D)."""
 
-    def __init__(self, ld, nr, nc, index):
+    def __init__(self, ld, nr, nc, index, keep=None, pos=None):
         self.ld, self.nr, self.nc = ld, int(nr), int(nc)
         self.index = np.asarray(index, dtype=np.int64)
         if len(self.index) != self.nr + self.nc:
             raise ValueError("a %d x %d coupling needs %d halo rows, not %d"
                              % (self.nr, self.nc, self.nr + self.nc, len(self.index)))
+        self.keep = None if keep is None else np.asarray(keep, dtype=np.int32)
+        self.pos = None if pos is None else np.asarray(pos, dtype=np.float64)
+        if self.keep is not None and len(self.keep) != self.nr:
+            raise ValueError("a %d x %d coupling needs %d kept-column counts, not %d"
+                             % (self.nr, self.nc, self.nr, len(self.keep)))
+        if self.pos is not None and (self.keep is None or len(self.pos) != self.nr + self.nc):
+            raise ValueError("a tapered %d x %d coupling needs its kept-column counts and %d halo "
+                             "positions" % (self.nr, self.nc, self.nr + self.nc))
 
     def rows(self):
         """The halo's packed rows, (nr + nc, ceil(N / 4)) uint8."""
@@ -491,12 +650,22 @@ class GenoCoupling:
         G, _ = self.ld._standardise(self.rows(), lambda counts: self._check(gb, counts))
         C = G[:self.nr] @ G[self.nr:].T
         a, c = np.arange(self.nr)[:, None], np.arange(self.nc)[None, :]
+        if self.keep is not None:
+            if self.pos is not None:
+                w = 1.0 - (self.pos[self.nr:][None, :] - self.pos[:self.nr][:, None]) / self.ld._span
+                C = C * w
+            return np.where(c < self.keep[:, None], C, 0.0)
         C[c + self.nr - a > self.ld.window] = 0.0
         return C
 
     def upload(self, eng, ld, gb):
         """Register the coupling on the engine (every rank, every coupling: the
         rows are read only where the rank owns one of the two pieces)."""
+        if self.keep is not None:
+            eng.geno_coupling_reach(ld, gb, self.nr, self.nc, self.rows, self.ld.panel.N,
+                                    self.keep, self.pos, self.ld._span,
+                                    check=lambda counts: self._check(gb, counts))
+            return
         eng.geno_coupling(ld, gb, self.nr, self.nc, self.rows, self.ld.panel.N, self.ld.window,
                           check=lambda counts: self._check(gb, counts))
 
@@ -515,15 +684,76 @@ def check_ld_window(window):
     return w
 
 
-def load_bed_ld(path, s, block_size=None, blocks_file=None, variants=None, window=None):
-    """A .bed panel as a BedLD: blocks of block_size markers (the last shorter) or
-    the sizes listed one per line in blocks_file; variants: the marker order as
-    variant ids (default: the panel's own); window: keep only LD within that many
-    markers of the diagonal, as packed bands (BedLD)."""
+def check_ld_distance(x, unit):
+    """An LD window by distance as a positive finite float (None: none)."""
+    if x is None:
+        return None
+    try:
+        v = float(x)
+        ok = np.isfinite(v) and v > 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("the LD window in %s must be a positive number, not %r" % (unit, x))
+    return v
+
+
+LD_TAPERS = ("none", "triangle")
+
+
+def check_ld_taper(taper):
+    """"triangle" or None (given as None or "none"); ValueError otherwise."""
+    if taper is None or taper == "none":
+        return None
+    if taper not in LD_TAPERS:
+        raise ValueError("the LD taper must be one of %s, not %r" % (", ".join(LD_TAPERS), taper))
+    return taper
+
+
+def reach_masked(R, hi, pos=None, span=None):
+    """The distance-windowed block of a symmetric R (include/sgvamp_hip.h): for j
+    >= i the entry (i, j) where j <= hi[i], times 1.0 - (pos[j] - pos[i]) / span
+    where pos is given, exactly 0.0 elsewhere; the lower triangle its mirror."""
+    n = R.shape[0]
+    i = np.arange(n)
+    up = (i[None, :] >= i[:, None]) & (i[None, :] <= np.asarray(hi)[:, None])
+    U = np.asarray(R, dtype=np.float64)
+    if pos is not None:
+        p = np.asarray(pos, dtype=np.float64)
+        U = U * (1.0 - (p[None, :] - p[:, None]) / float(span))
+    U = np.where(up, U, 0.0)
+    return U + np.triu(U, 1).T
+
+
+def chromosome_blocks(panel, select=None):
+    """LD block sizes, one block per run of equal chromosome code in the run's
+    marker order (``select``: panel rows in that order; default the panel's own)."""
+    if panel.chrom is None:
+        raise ValueError("the panel %s carries no chromosome column" % panel.prefix)
+    chrom = panel.chrom if select is None else [panel.chrom[int(i)] for i in select]
+    sizes = []
+    for k, c in enumerate(chrom):
+        if k and c == chrom[k - 1]:
+            sizes[-1] += 1
+        else:
+            sizes.append(1)
+    return sizes
+
+
+def load_bed_ld(path, s, block_size=None, blocks_file=None, variants=None, window=None,
+                window_kb=None, window_cm=None, taper=None, chr_blocks=False):
+    """A .bed panel as a BedLD: blocks of block_size markers (the last shorter),
+    the sizes listed one per line in blocks_file, or (chr_blocks) one block per
+    run of equal chromosome code; variants: the marker order as variant ids
+    (default: the panel's own); window: keep only LD within that many markers of
+    the diagonal, as packed bands; window_kb / window_cm: within that distance by
+    the .bim's positions; taper: "triangle" (BedLD)."""
     panel = read_bed(path)
     select = None if variants is None else panel.index_of(list(variants))
     M = panel.M if select is None else len(select)
-    if blocks_file is not None:
+    if chr_blocks:
+        sizes = chromosome_blocks(panel, select)
+    elif blocks_file is not None:
         with open(blocks_file) as f:
             sizes = [int(t) for t in f.read().split()]
         if sum(sizes) != M:
@@ -531,4 +761,5 @@ def load_bed_ld(path, s, block_size=None, blocks_file=None, variants=None, windo
                              % (blocks_file, sum(sizes), M))
     else:
         sizes = equal_blocks(M, block_size)
-    return BedLD(panel, sizes, select=select, s=s, window=window)
+    return BedLD(panel, sizes, select=select, s=s, window=window, window_kb=window_kb,
+                 window_cm=window_cm, taper=taper)

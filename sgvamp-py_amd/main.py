@@ -31,9 +31,17 @@ Same flags, defaults, validation messages, log lines and output files
   device, cut into coupled pieces like any windowed LD (sgvamp.BAND_PIECE).
   Truncated LD need not be positive semi-definite (as with PLINK's --ld-window);
   --s is the remedy.  It needs packed LD storage (--ld-packing on, the default).
+  --ld-window-kb X / --ld-window-cm X limit the LD by distance instead, by the
+  .bim's base-pair or cM column (with --ld-window as well both limits apply);
+  --ld-taper triangle multiplies the LD of two markers d apart by 1 - d / D, D
+  the one window given, which keeps the windowed LD positive semi-definite, so
+  --s 0 works.  --ld-chr-blocks makes one LD block per chromosome of the .bim (a
+  third way to give the blocks): positions restart at a chromosome, so a distance
+  window must not cross one.
 """
 import argparse
 import logging
+import math
 import os
 import sys
 import time
@@ -95,17 +103,30 @@ def build_parser():
                         help="With a .bed LD source: file listing the LD block sizes, one per line")
     parser.add_argument("--ld-window", default=None,
                         help="With a .bed LD source: keep only the LD between markers at most this many markers apart (in the run's marker order, inside each LD block) and store the blocks as packed bands formed on the device; a window does not preserve positive semi-definiteness, --s is the remedy")
+    parser.add_argument("--ld-window-kb", default=None,
+                        help="With a .bed LD source: keep only the LD between markers at most this many kilobases apart by the .bim's base-pair column (inside each LD block, where the positions must not decrease); combines with --ld-window, both limits then apply; stored as packed bands as wide as the farthest reach")
+    parser.add_argument("--ld-window-cm", default=None,
+                        help="With a .bed LD source: as --ld-window-kb, in centimorgans of the .bim's genetic-position column")
+    parser.add_argument("--ld-taper", choices=["none", "triangle"], default="none",
+                        help="With exactly one of --ld-window / --ld-window-kb / --ld-window-cm: triangle multiplies the LD of two markers a distance d apart by 1 - d / D (D the window; W + 1 markers for --ld-window W), which keeps the windowed LD positive semi-definite, so --s 0 works")
+    parser.add_argument("--ld-chr-blocks", action="store_true",
+                        help="With a .bed LD source: one LD block per run of equal chromosome code in the run's marker order (instead of --ld-block-size / --ld-blocks)")
     parser.add_argument("--ld-packing", choices=["on", "off"], default="on",
                         help="Packed storage of symmetric LD blocks (on, the default) or full dense squares (off)")
     return parser
 
 
 def check_bed_flags(parser, args):
-    """A .bed LD source needs exactly one of --ld-block-size / --ld-blocks; the
-    flags mean nothing without one."""
+    """A .bed LD source needs exactly one of --ld-block-size / --ld-blocks /
+    --ld-chr-blocks; the flags mean nothing without one."""
     bed = any(p.endswith(".bed") for p in (args.ld_files or "").split(","))
     given = (args.ld_block_size is not None) + (args.ld_blocks is not None)
-    if bed and given == 0:
+    if args.ld_chr_blocks:
+        if not bed:
+            parser.error("--ld-chr-blocks applies to a .bed LD source only")
+        if given:
+            parser.error("--ld-chr-blocks, --ld-block-size and --ld-blocks exclude each other: give exactly one")
+    if bed and given == 0 and not args.ld_chr_blocks:
         parser.error("a .bed LD source needs its LD blocks: give --ld-block-size n or --ld-blocks FILE")
     if given == 2:
         parser.error("--ld-block-size and --ld-blocks exclude each other: give exactly one")
@@ -129,6 +150,30 @@ def check_bed_flags(parser, args):
             parser.error("--ld-window must be a positive integer (markers), not %r" % (args.ld_window,))
         if args.ld_packing == "off":
             parser.error("--ld-window stores packed bands: it cannot be combined with --ld-packing off")
+    for flag, val in (("--ld-window-kb", args.ld_window_kb), ("--ld-window-cm", args.ld_window_cm)):
+        if val is None:
+            continue
+        if not bed:
+            parser.error("%s applies to a .bed LD source only" % flag)
+        try:
+            ok = math.isfinite(float(val)) and float(val) > 0
+        except ValueError:
+            ok = False
+        if not ok:
+            parser.error("%s must be a positive number, not %r" % (flag, val))
+        if args.ld_packing == "off":
+            parser.error("%s stores packed bands: it cannot be combined with --ld-packing off" % flag)
+    if args.ld_window_kb is not None and args.ld_window_cm is not None:
+        parser.error("--ld-window-kb and --ld-window-cm exclude each other: give one distance")
+    if args.ld_taper != "none":
+        windows = sum(w is not None for w in (args.ld_window, args.ld_window_kb, args.ld_window_cm))
+        if not bed:
+            parser.error("--ld-taper applies to a .bed LD source only")
+        if windows != 1:
+            parser.error("--ld-taper needs exactly one of --ld-window / --ld-window-kb / "
+                         "--ld-window-cm as its distance: %d given" % windows)
+        if args.ld_packing == "off":
+            parser.error("--ld-taper stores packed bands: it cannot be combined with --ld-packing off")
 
 
 def pip_threshold_arg(text):
@@ -258,7 +303,10 @@ def main(argv=None):
                     by_path[p] = load_bed_ld(
                         p, s, block_size=args.ld_block_size, blocks_file=args.ld_blocks,
                         variants=bim_ref if bim_fpaths is not None else None,
-                        window=None if args.ld_window is None else int(args.ld_window))
+                        window=None if args.ld_window is None else int(args.ld_window),
+                        window_kb=None if args.ld_window_kb is None else float(args.ld_window_kb),
+                        window_cm=None if args.ld_window_cm is None else float(args.ld_window_cm),
+                        taper=args.ld_taper, chr_blocks=args.ld_chr_blocks)
                 else:
                     by_path[p] = load_ld(p, s)
             lds.append(by_path[p])
