@@ -162,7 +162,8 @@ int sgv_set_cg_exact(sgv_ctx* ctx, int mode);
  * the bytes per pass: the LD matrix of src/main.py:199-265 is symmetric by
  * construction, R = X^T X); mode 0 always stores the full square. */
 int sgv_set_ld_packing(sgv_ctx* ctx, int mode);
-/* fmt_out: 0 dense, 1 packed symmetric (triangle), 2 packed band, -1 not set. */
+/* fmt_out: 0 dense, 1 packed symmetric (triangle), 2 packed band, 3 factor
+ * (sgv_geno_ld_factor), -1 not set. */
 int sgv_ld_block_format(sgv_ctx* ctx, int ld, int blk_local, int* fmt_out);
 /* Element type of PACKED blocks (triangle or band: symmetric blocks through
  * sgv_set_ld_block with packing on, every sgv_set_ld_block_csr block, the
@@ -288,6 +289,42 @@ int sgv_geno_ld(sgv_ctx* ctx, int ld, int blk_local);
 int sgv_geno_r(sgv_ctx* ctx, int k, const double* y);
 int sgv_geno_g(sgv_ctx* ctx, const double* beta_local, double* g_blocks_out);
 int sgv_geno_clear(sgv_ctx* ctx);
+
+/* ---- factor LD blocks: R_b p applied as G_b (G_b^T p) from the 2-bit rows -----
+ * sgv_geno_ld_factor: block blk_local of LD matrix ld becomes a factor block of
+ * exactly the G defined above (same integer counts, mean, sd, mean imputation,
+ * G[i][n] = lut_i[code_in]).  No R_b is formed or stored: every LD pass (CG, the
+ * warm-start residual, the gamw pass, sgv_ld_matvec, sgv_ld_pass_ex) applies
+ *   t = G_b^T P (nsamp x ncol), Q = G_b t (n_b x ncol)
+ * and then the epilogue of every other form (out = c1 Q + c2 in, the optional
+ * yout, the dot partials in block order), so R_b = G_b G_b^T is positive semi-
+ * definite by construction and the ridge works through c1 / c2 as always.  The
+ * block holds 2 bits per genotype (the rows at their stride of whole 32-bit
+ * words) plus 32 bytes of table per marker.  Every sum has a fixed order that is
+ * a function of (n_b, nsamp, ncol) alone (csrc/geno_factor.hip), so results are
+ * bitwise the same for every rank count and whatever else is in the launch.
+ * The call TAKES OVER the rows and tables staged by sgv_geno_set_block for the
+ * block (a hand-over: nothing is computed or copied); the staged block is empty
+ * afterwards, so another panel can be staged for the same block of another LD
+ * matrix (cohorts with distinct panels), and sgv_geno_r / sgv_geno_g need a fresh
+ * sgv_geno_set_block -- or must run before this call.  sgv_destroy, and a later
+ * sgv_geno_ld_factor for the same block, release what was taken over;
+ * sgv_geno_clear does not touch it.
+ * One form per LD matrix: SGV_ERR_STATE, with the stored block (if any) left as
+ * it was, when the block has no staged genotypes, when a marker has no LD, when
+ * the matrix already holds a block of another form or a coupling -- and from
+ * sgv_set_ld_block, sgv_set_ld_block_csr, sgv_set_ld_coupling, sgv_synth_ld_g and
+ * every sgv_geno_ld* / sgv_geno_coupling* on a matrix that holds factor blocks.
+ * There is no window, taper, coupling or f32 storage of this form
+ * (sgv_set_ld_precision and sgv_set_ld_packing do not apply), and
+ * sgv_get_ld_block is SGV_ERR_STATE: there is no R to download.
+ * sgv_ld_block_format reports 3, sgv_ld_block_precision 64, sgv_ld_stored_bytes
+ * and sgv_timers t[2] the bytes a pass reads (rows at their stride + tables);
+ * t[6] counts 2 ncol (2 nsamp n_b) flops per block and pass, t[5] the scratch
+ * written and read (t and the first product's slab partials).  The scratch is
+ * the context's: at most 256 MB, or one block's (ceil(n_b / 1024) + 1) nsamp 128
+ * bytes where that is more.  sgv_ld_pass_form reports SGV_KIND_FACTOR. */
+int sgv_geno_ld_factor(sgv_ctx* ctx, int ld, int blk_local);
 
 /* ---- windowed genotype LD: packed bands and their couplings from the bits ---
  * With a window W >= 1, counted in markers of the run's marker order (block-
@@ -695,6 +732,9 @@ int sgv_em_cost_model(double cohort_markers, int nranks, double latency_us, doub
 #define SGV_KIND_WIDE 4
 #define SGV_KIND_STRIP16 5
 #define SGV_KIND_WALK 6
+#define SGV_KIND_FACTOR 7   /* a factor matrix (sgv_geno_ld_factor): the VALU f64 kernels of
+                             * csrc/geno_factor.hip at every column count; every other field
+                             * of the form is 0 (valu_class -1); never sgv_pass_form_model's answer */
 #define SGV_PF_KIND 0
 #define SGV_PF_VALU_CLASS 1
 #define SGV_PF_REST_KIND 2

@@ -427,6 +427,8 @@ extern "C" void sgv_destroy(sgv_ctx* c) {
   if (c->d_halo) (void)hipFree(c->d_halo);
   if (c->h_halo) (void)hipHostFree(c->h_halo);
   if (c->d_rowpart) (void)hipFree(c->d_rowpart);
+  if (c->d_ft) (void)hipFree(c->d_ft);
+  if (c->d_ftp) (void)hipFree(c->d_ftp);
   if (c->d_whead) (void)hipFree(c->d_whead);
   if (c->d_wcarry) (void)hipFree(c->d_wcarry);
   if (c->d_colpart) (void)hipFree(c->d_colpart);
@@ -783,6 +785,49 @@ extern "C" int sgv_geno_ld(sgv_ctx* c, int ld, int b) {
   const LdBlock& lb = c->ldb[ld][b];
   HIPCHK(launch_bed_syrk(gb.d_bits, gb.stride_w, gb.d_lut, (int)c->bn[b], gb.nsamp, lb.ptr,
                          c->lda[b], lb.fmt, lb.d_poff, lb.d_pw, lb.bits, c->st));
+  CHK(stream_wait(c));
+  std::fill(c->rx0_valid.begin(), c->rx0_valid.end(), 0);
+  return SGV_OK;
+}
+
+// Block b of LD matrix ld becomes a factor block (ldplan.hip: ld_pass applies G_b
+// (G_b^T p) from the rows): the staged rows and tables change owner, nothing is
+// computed or copied.  Every refusal comes before any storage changes.
+extern "C" int sgv_geno_ld_factor(sgv_ctx* c, int ld, int b) {
+  ENTER(c);
+  if (ld < 0 || ld >= c->nld || b < 0 || b >= c->nblk)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_ld_factor: bad arguments (ld %d, block %d)", ld, b);
+  if ((int)c->geno.size() != c->nblk || !c->geno[b].d_bits)
+    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_factor: block %d has no genotypes "
+                "(sgv_geno_set_block; an earlier sgv_geno_ld_factor took them over)", b);
+  GenoBlock& gb = c->geno[b];
+  if (gb.nbad)
+    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_factor: block %d has %lld marker(s) without LD "
+                "(monomorphic or unobserved)", b, (long long)gb.nbad);
+  for (int o = 0; o < c->nblk; ++o)
+    if (c->ldb[ld][o].ptr && c->ldb[ld][o].fmt != 3)
+      return fail(c, SGV_ERR_STATE, "sgv_geno_ld_factor: LD matrix %d holds a stored block "
+                  "(block %d): one form per LD matrix", ld, o);
+  if (!c->cpl[ld].empty())
+    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_factor: LD matrix %d has couplings (band pieces); "
+                "a factor matrix has none", ld);
+  CHK(stream_wait(c));   // no pass still reads the block this one replaces
+  LdBlock& lb = c->ldb[ld][b];
+  free_block(lb);
+  c->plan[ld].valid = false;
+  const double n = (double)c->bn[b];
+  lb.fmt = 3;
+  lb.bits = 64;
+  lb.ptr = reinterpret_cast<double*>(gb.d_bits);
+  lb.g_lut = gb.d_lut;
+  lb.g_msd = gb.d_msd;
+  lb.g_stride_w = gb.stride_w;
+  lb.g_nsamp = gb.nsamp;
+  lb.stored_bytes = n * (double)gb.stride_w * 4.0 + n * 4.0 * 8.0;
+  lb.stored_elems = 2.0 * (double)gb.nsamp * n;
+  gb = GenoBlock();      // the staged block is empty: its buffers are the LD block's now
+  BlkDesc d{nullptr, c->lda[b], c->bn[b], c->bvoff[b]};
+  HIPCHK(hipMemcpyAsync(c->d_blks[ld] + b, &d, sizeof d, hipMemcpyHostToDevice, c->st));
   CHK(stream_wait(c));
   std::fill(c->rx0_valid.begin(), c->rx0_valid.end(), 0);
   return SGV_OK;

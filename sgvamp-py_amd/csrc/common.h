@@ -754,4 +754,31 @@ hipError_t launch_bed_row_dot(const uint32_t* d_bits, int64_t stride_w, const do
 hipError_t launch_bed_g_accum(const uint32_t* d_bits, int64_t stride_w, const double* d_msd, int n,
                               int nsamp, const double* d_beta, double* d_g, hipStream_t st);
 
+// ---- factor LD blocks (geno_factor.hip): R_b p applied as G_b (G_b^T p) from the
+// 2-bit rows, R_b never formed ------------------------------------------------
+constexpr int GF_SLAB = 1024;   // markers per slab of the first product (one partial t each)
+constexpr int GF_TILE = 64;     // markers per workgroup of the second product (one partial slot)
+constexpr int GF_SCH = 256;     // samples per workgroup of the first product
+constexpr int GF_QCH = 4;       // sample chunks of the second product (one wave each)
+// one factor block of a launch; tbase / pbase count doubles per column from the
+// start of the launch's scratch: t [nsamp][nc] at tbase * nc, the slab partials
+// [nslab][nc][nsamp] at pbase * nc
+struct FacBlock {
+  const uint32_t* bits;   // [n][stride_w]
+  const double* lut;      // [n][4]
+  int64_t stride_w;
+  int64_t voff;           // the block's offset in the padded vector layout
+  int64_t tbase, pbase;
+  int32_t n, nsamp;
+  int32_t nslab;          // ceil(n / GF_SLAB)
+  int32_t part0;          // first partial slot: tile k's dots go to part0 + k
+};
+// One pass over blocks fb[0 .. nfb): P interleaved into d_pk ([voff + i][nc], at
+// least Mpad x nc doubles), t = G^T P (slab partials, then their sum in
+// slab order), then Q = G t with the fused epilogue and the tiles' dot partials.
+// gx_t / gy_t / gx_q: the most sample chunks, slabs and tiles of any of the blocks
+hipError_t launch_geno_factor(int nc, const FacBlock* d_fb, int nfb, int gx_t, int gy_t, int gx_q,
+                              const PassArgs& pa, double* d_pk, double* d_t, double* d_tp,
+                              double* d_part, hipStream_t st);
+
 }  // namespace sgv

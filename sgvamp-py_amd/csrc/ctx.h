@@ -34,7 +34,8 @@ using namespace sgv;
 // one LD block of one LD matrix
 struct LdBlock {
   double* ptr = nullptr;       // the allocation; a packed block with bits = 32 holds floats (f32())
-  int fmt = 0;                 // 0: dense n x lda row-major; 1: packed symmetric panels
+  int fmt = 0;                 // 0: dense n x lda row-major; 1: packed symmetric panels;
+                               // 3: factor (sgv_geno_ld_factor): ptr is the block's 2-bit rows
   int bits = 64;               // stored element type: 64, or 32 (packed blocks only,
                                // sgv_set_ld_precision): same panels and strides, in elements
   float* f32() const { return reinterpret_cast<float*>(ptr); }
@@ -48,6 +49,14 @@ struct LdBlock {
   double stored_bytes = 0.0;   // bytes a pass reads: n^2*8 dense, sum H_g (n - r0_g)*8 packed
                                // (* 4 at bits = 32): stored_elems * esz()
   double stored_elems = 0.0;   // elements a pass reads
+  // factor block: the rows ([n][g_stride_w] 32-bit words, owned through ptr) and the
+  // tables taken over from sgv_geno_set_block; stored_bytes = the rows at their
+  // stride plus g_lut, stored_elems = the 2 N n multiply-adds per column
+  double* g_lut = nullptr;     // [n][4]
+  double* g_msd = nullptr;     // [n][2]
+  int64_t g_stride_w = 0;
+  int g_nsamp = 0;
+  const uint32_t* g_bits() const { return reinterpret_cast<const uint32_t*>(ptr); }
 };
 
 // coupling between consecutive band pieces gb and gb + 1 of one LD matrix (a
@@ -135,6 +144,17 @@ struct LdPlan {
   int64_t hmax = 0, h_src0 = 0, h_src1 = 0;
   int h_len0 = 0, h_len1 = 0;
   double cpl_bytes = 0.0;      // coupling matrix bytes read per pass (this rank)
+  // factor matrix (every block fmt 3; ldplan.hip: plan_form): the blocks' descriptors and
+  // their launches -- consecutive blocks whose t and slab partials fit the
+  // context's scratch at 16 columns (GF_SCRATCH_MAX), at least one block each
+  struct FacLaunch {
+    int b0, nb;                // blocks [b0, b0 + nb)
+    int gx_t, gy_t, gx_q;      // most sample chunks, slabs, tiles of any of them
+  };
+  bool factor = false;
+  FacBlock* d_fac = nullptr;
+  std::vector<FacLaunch> fac_launch;
+  double fac_scratch = 0.0;    // doubles per column written and read per pass (t + slab partials)
 };
 
 // default number of right-hand sides from which packed passes run on the f64
@@ -216,6 +236,11 @@ struct sgv_ctx {
   double* d_rowpart = nullptr;   // k_sym_pass row partials
   double* d_colpart = nullptr;   // k_sym_pass column partials
   size_t rowpart_cap = 0, colpart_cap = 0, part_cap = 0;
+  // factor blocks: t = G^T P ([nsamp][nc] per block of a launch) and the first
+  // product's slab partials ([nslab][nc][nsamp] per block); sized by ensure_plan
+  double* d_ft = nullptr;
+  double* d_ftp = nullptr;
+  size_t ft_cap = 0, ftp_cap = 0;
   int mfma_min = 3;              // see mfma_min_default
   double* d_pk = nullptr;        // RHS interleaved [Mpad][16] for the MFMA pass
   // asynchronous per-iteration outputs (xhat1, r1[k]): device pack buffer and two

@@ -26,6 +26,7 @@ void free_plan(LdPlan& p){
   if (p.d_wpanels) (void)hipFree(p.d_wpanels);
   if (p.d_witems) (void)hipFree(p.d_witems);
   if (p.d_wfins) (void)hipFree(p.d_wfins);
+  if (p.d_fac) (void)hipFree(p.d_fac);
   p = LdPlan();
 }
 
@@ -33,6 +34,8 @@ void free_block(LdBlock& lb){
   if (lb.ptr) (void)hipFree(lb.ptr);
   if (lb.d_poff) (void)hipFree(lb.d_poff);
   if (lb.d_pw) (void)hipFree(lb.d_pw);
+  if (lb.g_lut) (void)hipFree(lb.g_lut);   // a factor block's tables (its rows are ptr)
+  if (lb.g_msd) (void)hipFree(lb.g_msd);
   lb = LdBlock();
 }
 
@@ -46,6 +49,10 @@ static int64_t panel_ext(int64_t n, int64_t r0, int64_t ext) {
 // element type (sgv_set_ld_precision); the full square is always f64
 int ld_alloc(sgv_ctx* c, int ld, int b, int fmt, int64_t ext){
   LdBlock& lb = c->ldb[ld][b];
+  for (int o = 0; o < c->nblk; ++o)   // one form per LD matrix; before any storage changes
+    if (c->ldb[ld][o].ptr && c->ldb[ld][o].fmt == 3)
+      return fail(c, SGV_ERR_STATE, "LD matrix %d holds factor blocks (block %d, "
+                  "sgv_geno_ld_factor): a stored block cannot join them", ld, o);
   if (fmt == 0) ext = 0;
   const int bits = fmt == 1 ? c->ld_bits : 64;
   if (lb.ptr && lb.fmt == fmt && lb.ext == ext && lb.bits == bits) return SGV_OK;
@@ -572,6 +579,78 @@ static int plan_couplings(sgv_ctx* c, int ld, LdPlan& pl, std::vector<int>& slot
   return SGV_OK;
 }
 
+// Scratch of one factor launch at 16 columns, in doubles: 256 MB.  At the north
+// star (64 x 15,625 markers, N = 10,000) a block needs 16 slabs x 10,000 x 16 + 10,000
+// x 16 doubles = 21.8 MB, so a launch holds 11 blocks and the scratch is 240 MB
+// beside 2.5 GB of rows; one block larger than this gets a launch of its own.
+constexpr double GF_SCRATCH_MAX = 32.0 * 1024 * 1024;
+
+// The plan of a factor matrix (every block fmt 3): block descriptors, one partial
+// slot per GF_TILE markers in block order, and the launches.  How the blocks are
+// cut into launches changes no sum: a block's t, slabs, tiles and slots are its own.
+static int plan_factor(sgv_ctx* c, int ld) {
+  LdPlan& pl = c->plan[ld];
+  for (int b = 0; b < c->nblk; ++b)
+    if (c->ldb[ld][b].fmt != 3)
+      return fail(c, SGV_ERR_STATE, "LD matrix %d mixes factor and stored blocks (block %d)", ld, b);
+  if (!c->cpl[ld].empty())
+    return fail(c, SGV_ERR_STATE, "LD matrix %d: couplings on a factor matrix", ld);
+  pl.factor = true;
+  pl.bits = 64;
+  std::vector<FacBlock> fb(c->nblk);
+  std::vector<int> pbeg(c->nblk + 1, 0);
+  int nparts = 0;
+  double tneed = 0.0, pneed = 0.0, tcur = 0.0, pcur = 0.0;
+  for (int b = 0; b < c->nblk; ++b) {
+    const LdBlock& lb = c->ldb[ld][b];
+    const int64_t n = c->bn[b];
+    if (n >= ((int64_t)1 << 31) - GF_SLAB)
+      return fail(c, SGV_ERR_ARG, "LD matrix %d block %d: %lld markers in one factor block", ld, b,
+                  (long long)n);
+    FacBlock& f = fb[b];
+    f.bits = lb.g_bits();
+    f.lut = lb.g_lut;
+    f.stride_w = lb.g_stride_w;
+    f.voff = c->bvoff[b];
+    f.n = (int32_t)n;
+    f.nsamp = lb.g_nsamp;
+    f.nslab = (int32_t)((n + GF_SLAB - 1) / GF_SLAB);
+    f.part0 = nparts;
+    pbeg[b] = nparts;
+    nparts += (int)((n + GF_TILE - 1) / GF_TILE);
+    const double tb = (double)f.nsamp, pb = (double)f.nslab * (double)f.nsamp;
+    if (pl.fac_launch.empty() || (tcur + pcur + tb + pb) * MAXC > GF_SCRATCH_MAX) {
+      pl.fac_launch.push_back(LdPlan::FacLaunch{b, 0, 0, 0, 0});
+      tcur = pcur = 0.0;
+    }
+    LdPlan::FacLaunch& fl = pl.fac_launch.back();
+    f.tbase = (int64_t)tcur;
+    f.pbase = (int64_t)pcur;
+    tcur += tb;
+    pcur += pb;
+    tneed = std::max(tneed, tcur);
+    pneed = std::max(pneed, pcur);
+    ++fl.nb;
+    fl.gx_t = std::max(fl.gx_t, (f.nsamp + GF_SCH - 1) / GF_SCH);
+    fl.gy_t = std::max(fl.gy_t, (int)f.nslab);
+    fl.gx_q = std::max(fl.gx_q, (int)((n + GF_TILE - 1) / GF_TILE));
+    pl.fac_scratch += tb + pb;
+    pl.stored_bytes += lb.stored_bytes;
+    pl.dense_bytes += (double)n * (double)n * 8.0;
+    pl.mac_elems += lb.stored_elems;   // 2 N n_b multiply-adds per column
+  }
+  pbeg[c->nblk] = nparts;
+  pl.nparts = nparts;
+  CHK(upload_table(c, fb, &pl.d_fac));
+  CHK(upload_table(c, pbeg, &pl.d_pbeg));
+  CHK(grow(c, &c->d_ft, &c->ft_cap, (size_t)tneed * MAXC));
+  CHK(grow(c, &c->d_ftp, &c->ftp_cap, (size_t)pneed * MAXC));
+  CHK(grow(c, &c->d_pk, &c->pk_cap, (size_t)c->Mpad * 16));
+  CHK(grow(c, &c->d_part, &c->part_cap, (size_t)nparts * MAXC));
+  pl.valid = true;
+  return SGV_OK;
+}
+
 // launch tables of LD matrix ld: dense row groups, packed (panel, chunk) items
 // per chunk-width class, panels; unified partial slots in block order
 int ensure_plan(sgv_ctx* c, int ld){
@@ -593,6 +672,8 @@ int ensure_plan(sgv_ctx* c, int ld){
     }
     pl.bits = first >= 0 ? c->ldb[ld][first].bits : 64;
   }
+  for (int b = 0; b < c->nblk; ++b)
+    if (c->ldb[ld][b].fmt == 3) return plan_factor(c, ld);   // every block is one (ld_alloc)
   const bool f32 = pl.bits == 32;   // every pass on the 512-column strips (pass_form; A/B: walks)
   const PassSwitches sw = read_pass_switches();
   const int pair_forced = plan_pair_forced(sw);
@@ -755,11 +836,23 @@ static PlanShape plan_shape(const LdPlan& pl) {
   return ps;
 }
 
+// The form of a pass over a built plan.  Whether the matrix is a factor matrix is
+// this one predicate on the plan, decided here and nowhere else; the stored
+// forms are pass_form's decision over the plan's shape.
+static PassForm plan_form(const LdPlan& pl, int nc, int mfma_min) {
+  if (pl.factor) {
+    PassForm f;
+    f.kind = PK_FACTOR;
+    return f;
+  }
+  return pass_form(plan_shape(pl), nc, mfma_min, read_pass_switches());
+}
+
 int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
   if (nc <= 0) return SGV_OK;
   CHK(ensure_plan(c, ld));
   const LdPlan& pl = c->plan[ld];
-  const PassForm f = pass_form(plan_shape(pl), nc, c->mfma_min, read_pass_switches());
+  const PassForm f = plan_form(pl, nc, c->mfma_min);
   PassArgs pa = pa_in;
   pa.cpbuf = c->d_cpbuf;
   hipEvent_t e0, e1;
@@ -773,6 +866,13 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
     c->evpool.pop_back();
   }
   HIPCHK(hipEventRecord(e0, c->st));
+  if (f.kind == PK_FACTOR) {   // before the stored forms: the plan holds nothing of theirs
+    for (const LdPlan::FacLaunch& fl : pl.fac_launch)   // stream order: the scratch is reused
+      HIPCHK(launch_geno_factor(nc, pl.d_fac + fl.b0, fl.nb, fl.gx_t, fl.gy_t, fl.gx_q, pa, c->d_pk,
+                                c->d_ft, c->d_ftp, c->d_part, c->st));
+    // t, the slab partials and the interleaved right-hand sides, written and read
+    c->aux_bytes += 2.0 * 8.0 * nc * (pl.fac_scratch + (double)c->Mloc);
+  }
   if (pl.halo || pl.nctasks) CHK(coupling_pass(c, pl, nc, pa));
   if (f.dense) HIPCHK(launch_ld_pass(nc, c->d_blks[ld], pl.d_rg, pl.nrg, pa, c->d_part, c->st));
   if (f.kind == PK_VALU) {
@@ -783,7 +883,7 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
                                c->d_colpart, c->d_part, c->st));
     const double cw = (double)(1024 >> cls);
     c->aux_bytes += 2.0 * 8.0 * nc * (double)pl.nitems[cls] * (SYM_H + cw);
-  } else if (f.kind != PK_NONE) {
+  } else if (f.kind != PK_NONE && f.kind != PK_FACTOR) {
     HIPCHK(launch_pk(pa, nc, c->Mpad, c->d_pk, f.pk_width, f.pk_paired, c->st));
     if (f.kind == PK_WALK) {   // band plan: the walks, then the head panels
       HIPCHK(launch_band_walk(nc, pl.d_walks, pl.nwalks, pl.d_wpanels, pl.d_witems, c->d_pk,
@@ -866,8 +966,7 @@ extern "C" int sgv_ld_pass_form(sgv_ctx* c, int ld, int ncol, int32_t* form, int
   if (ld < 0 || ld >= c->nld || ncol < 1 || ncol > MAXC || !form || cap < 0)
     return fail(c, SGV_ERR_ARG, "sgv_ld_pass_form: bad arguments");
   CHK(ensure_plan(c, ld));
-  pass_form_ints(pass_form(plan_shape(c->plan[ld]), ncol, c->mfma_min, read_pass_switches()),
-                 form, cap);
+  pass_form_ints(plan_form(c->plan[ld], ncol, c->mfma_min), form, cap);
   return SGV_OK;
 }
 
@@ -1036,6 +1135,9 @@ extern "C" int sgv_get_ld_block(sgv_ctx* c, int ld, int b, double* host, int64_t
   CHK(ld_ready(c, ld));
   const int64_t n = c->bn[b];
   const LdBlock& lb = c->ldb[ld][b];
+  if (lb.fmt == 3)
+    return fail(c, SGV_ERR_STATE, "sgv_get_ld_block: LD matrix %d block %d is a factor block "
+                "(sgv_geno_ld_factor): R is never formed; sgv_geno_ld stores it", ld, b);
   CHK(stream_wait(c));
   if (lb.fmt == 0) {
     HIPCHK(hipMemcpy2D(host, sizeof(double) * ld_host, lb.ptr, sizeof(double) * c->lda[b],
@@ -1072,7 +1174,7 @@ extern "C" int sgv_ld_block_format(sgv_ctx* c, int ld, int b, int* fmt_out) {
   if (ld < 0 || ld >= c->nld || b < 0 || b >= c->nblk || !fmt_out)
     return fail(c, SGV_ERR_ARG, "sgv_ld_block_format: bad arguments");
   const LdBlock& lb = c->ldb[ld][b];
-  *fmt_out = lb.ptr ? (lb.fmt == 1 && lb.ext > 0 ? 2 : lb.fmt) : -1;
+  *fmt_out = lb.ptr ? (lb.fmt == 1 && lb.ext > 0 ? 2 : lb.fmt) : -1;   // 3: factor
   return SGV_OK;
 }
 
@@ -1086,6 +1188,10 @@ int ld_set_coupling(sgv_ctx* c, const char* who, int ld, int gb, int nr, int nc,
   if ((la && nr > c->bn[ba]) || (lb && nc > c->bn[bb]))
     return fail(c, SGV_ERR_ARG, "%s: %d x %d exceeds the pieces", who, nr, nc);
   if ((la || lb) && !C) return fail(c, SGV_ERR_ARG, "%s: C is null", who);
+  for (int o = 0; o < c->nblk; ++o)
+    if (c->ldb[ld][o].ptr && c->ldb[ld][o].fmt == 3)
+      return fail(c, SGV_ERR_STATE, "%s: LD matrix %d holds factor blocks, which have no "
+                  "couplings", who, ld);
   std::vector<LdCoupling>& cv = c->cpl[ld];
   auto it = std::find_if(cv.begin(), cv.end(), [&](const LdCoupling& q) { return q.gb == gb; });
   if (it == cv.end()) {

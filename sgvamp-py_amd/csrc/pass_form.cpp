@@ -14,7 +14,8 @@ namespace sgv {
 
 static_assert(PK_NONE == SGV_KIND_NONE && PK_VALU == SGV_KIND_VALU && PK_STRIP4 == SGV_KIND_STRIP4 &&
                   PK_PAIR == SGV_KIND_PAIR && PK_WIDE == SGV_KIND_WIDE &&
-                  PK_STRIP16 == SGV_KIND_STRIP16 && PK_WALK == SGV_KIND_WALK,
+                  PK_STRIP16 == SGV_KIND_STRIP16 && PK_WALK == SGV_KIND_WALK &&
+                  PK_FACTOR == SGV_KIND_FACTOR,
               "the header names the kinds");
 
 // Band walks of up to 8 columns (two 4x4x4 column groups; 9-16 columns stay on

@@ -46,7 +46,9 @@ enum PackedKind {
   PK_PAIR = 3,      // wave-pair 512-column strips (k_sym_mfma_pair)
   PK_WIDE = 4,      // 1,024-column strips (k_sym_mfma_wide), `rest` behind them
   PK_STRIP16 = 5,   // 16x16x4 strips at 9-16 columns (k_sym_mfma16)
-  PK_WALK = 6       // band walks (k_band_walk)
+  PK_WALK = 6,      // band walks (k_band_walk)
+  PK_FACTOR = 7     // a factor matrix (geno_factor.hip): the plan's own predicate in ldplan.hip,
+                    // never pass_form's answer -- no PlanShape describes it
 };
 
 // Everything that selects a kernel instance or a launch argument of one pass

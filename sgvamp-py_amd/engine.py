@@ -246,6 +246,15 @@ class Engine:
             return
         self.ctx.sgv_geno_ld(int(ld), b_global - self.b0)
 
+    def geno_ld_factor(self, ld, b_global):
+        """Block b_global of LD matrix ld becomes a factor block (sgv_geno_ld_factor):
+        the staged rows and tables are handed over and every pass applies G_b (G_b^T
+        p).  The staged block is empty afterwards: geno_r / geno_g need a fresh
+        geno_set_block, or run before this."""
+        if not (self.b0 <= b_global < self.b1):
+            return
+        self.ctx.sgv_geno_ld_factor(int(ld), b_global - self.b0)
+
     def geno_ld_band(self, ld, b_global, window):
         """Windowed R_b of the staged genotypes (entries with |i - j| <= window, 0
         elsewhere) into LD matrix ld as a packed band (this rank's block; the

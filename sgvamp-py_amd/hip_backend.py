@@ -30,7 +30,7 @@ TIMERS_N, EXCHANGE_STATS_N, COMM_INFO_N = 10, 16, 5
 
 # sgv_ld_pass_form / sgv_pass_form_model (the header's SGV_KIND_*, SGV_PF_*, SGV_PS_*, SGV_SW_*,
 # in index order): the kinds by value, the form's fields, the shape's, the switches
-PASS_KINDS = ("none", "valu", "strip4", "pair", "wide", "strip16", "walk")
+PASS_KINDS = ("none", "valu", "strip4", "pair", "wide", "strip16", "walk", "factor")
 PASS_FORM_FIELDS = ("kind", "valu_class", "rest_kind", "load_form", "fin_form", "pk_width",
                     "pk_paired", "dense", "side", "rest_side", "mfma16", "idle_exit")
 PLAN_SHAPE_FIELDS = ("bits", "dense", "packed", "walks", "wide", "rest", "ragged", "pair",
@@ -88,6 +88,7 @@ _SIGS = {
     "sgv_synth_r": [_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, _c_dbl_p],
     "sgv_geno_set_block": [_vp, ctypes.c_int, _c_u8_p, ctypes.c_int64, ctypes.c_int, _c_i64_p],
     "sgv_geno_ld": [_vp, ctypes.c_int, ctypes.c_int],
+    "sgv_geno_ld_factor": [_vp, ctypes.c_int, ctypes.c_int],
     "sgv_geno_ld_band": [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64],
     "sgv_geno_coupling": [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_u8_p,
                           ctypes.c_int64, ctypes.c_int, ctypes.c_int64, _c_i64_p],

@@ -358,12 +358,32 @@ class BedLD(BlockLD):
     with a positive-definite function), so it needs no ridge.  A taper needs
     exactly one of the three windows; with ``window`` alone the positions are the
     markers' indices in the block and D = window + 1.  The band's width is the
-    widest reach, max(hi - i), per block and per piece."""
+    widest reach, max(hi - i), per block and per piece.
+
+    ``form`` = "stored" (default) forms and stores R_b as above.  "factor" keeps
+    the block as its 2-bit rows on the device and every LD pass applies R_b p as
+    G_b (G_b^T p) (include/sgvamp_hip.h, "factor LD blocks"): exactly positive
+    semi-definite, 2 bits per genotype instead of 8 bytes per pair of markers, so
+    an unwindowed block as long as a chromosome fits one GPU.  A factor source has
+    no window and no taper (ValueError), no pieces() and no regroup() onto another
+    partition (ValueError), and band_width() is None; block() stays the host's
+    dense G_b G_b^T, for checks."""
 
     uses_geno = True
+    FORMS = ("stored", "factor")
 
     def __init__(self, panel, block_sizes, select=None, s=0.0, window=None, window_kb=None,
-                 window_cm=None, taper=None, _pos=None):
+                 window_cm=None, taper=None, _pos=None, form="stored"):
+        if form not in self.FORMS:
+            raise ValueError("LD form must be 'stored' or 'factor', not %r" % (form,))
+        self.form = form
+        if form == "factor":
+            given = [n for n, v in (("window", window), ("window_kb", window_kb),
+                                    ("window_cm", window_cm), ("taper", check_ld_taper(taper)))
+                     if v is not None]
+            if given:
+                raise ValueError("the factor LD form applies the whole block G_b G_b^T: it takes "
+                                 "no %s" % " / ".join(given))
         sizes = [int(b) for b in block_sizes]
         super().__init__(block_sizes=sizes, loader=self._host_block, s=s)
         self.panel = panel
@@ -532,6 +552,12 @@ class BedLD(BlockLD):
     def upload(self, eng, ld, b, packed=True):
         """Stage block b's rows on the engine and form R_b there (this rank's
         blocks only; `packed` is the engine's own setting)."""
+        if self.form == "factor":     # the staged rows and tables become the block
+            if eng.b0 <= b < eng.b1:
+                counts = eng.geno_set_block(b, self.rows(b), self.panel.N)
+                self.check_counts(b, counts)
+                eng.geno_ld_factor(ld, b)
+            return
         if self.by_reach and not packed:
             raise ValueError("distance-windowed genotype LD is stored as a packed band: it needs "
                              "LD packing on")
@@ -560,6 +586,8 @@ class BedLD(BlockLD):
         sizes = [int(n) for ps in cuts for n in ps]
         if len(sizes) == len(self.block_sizes):
             return self, {}
+        if self.form == "factor":
+            raise ValueError("a factor LD source has no pieces: its blocks are applied whole")
         if self.window is None and not self.by_reach:
             raise ValueError("a genotype LD source without a window has dense blocks: no pieces")
         # by reach: the pieces keep the original blocks' positions (a tapered marker
@@ -597,6 +625,10 @@ class BedLD(BlockLD):
         dense-block limit."""
         if list(sizes) == list(self.block_sizes):
             return self
+        if self.form == "factor":
+            raise ValueError("a factor LD source cannot be regrouped onto another partition "
+                             "(%d blocks -> %d): no R exists to assemble; give every LD matrix "
+                             "of the run the same blocks" % (len(self.block_sizes), len(sizes)))
         L = super().regroup(sizes)
         if self.window is not None or self.by_reach:
             from sgvamp import _dense_guard
@@ -741,13 +773,13 @@ def chromosome_blocks(panel, select=None):
 
 
 def load_bed_ld(path, s, block_size=None, blocks_file=None, variants=None, window=None,
-                window_kb=None, window_cm=None, taper=None, chr_blocks=False):
+                window_kb=None, window_cm=None, taper=None, chr_blocks=False, form="stored"):
     """A .bed panel as a BedLD: blocks of block_size markers (the last shorter),
     the sizes listed one per line in blocks_file, or (chr_blocks) one block per
     run of equal chromosome code; variants: the marker order as variant ids
     (default: the panel's own); window: keep only LD within that many markers of
     the diagonal, as packed bands; window_kb / window_cm: within that distance by
-    the .bim's positions; taper: "triangle" (BedLD)."""
+    the .bim's positions; taper: "triangle"; form: "stored" or "factor" (BedLD)."""
     panel = read_bed(path)
     select = None if variants is None else panel.index_of(list(variants))
     M = panel.M if select is None else len(select)
@@ -762,4 +794,4 @@ def load_bed_ld(path, s, block_size=None, blocks_file=None, variants=None, windo
     else:
         sizes = equal_blocks(M, block_size)
     return BedLD(panel, sizes, select=select, s=s, window=window, window_kb=window_kb,
-                 window_cm=window_cm, taper=taper)
+                 window_cm=window_cm, taper=taper, form=form)

@@ -37,7 +37,12 @@ Same flags, defaults, validation messages, log lines and output files
   the one window given, which keeps the windowed LD positive semi-definite, so
   --s 0 works.  --ld-chr-blocks makes one LD block per chromosome of the .bim (a
   third way to give the blocks): positions restart at a chromosome, so a distance
-  window must not cross one.
+  window must not cross one.  --ld-form factor keeps every LD block as its 2-bit
+  genotype rows and applies R p as G (G^T p) in every LD pass instead of forming
+  and storing R (exactly positive semi-definite, 2 bits per genotype: a whole
+  chromosome as one unwindowed block fits one GPU); every --ld-files entry must
+  then be a .bed, and no window, taper, --ld-precision f32 or --ld-packing off
+  applies.  The default, --ld-form stored, is the run without the flag.
 """
 import argparse
 import logging
@@ -111,6 +116,8 @@ def build_parser():
                         help="With exactly one of --ld-window / --ld-window-kb / --ld-window-cm: triangle multiplies the LD of two markers a distance d apart by 1 - d / D (D the window; W + 1 markers for --ld-window W), which keeps the windowed LD positive semi-definite, so --s 0 works")
     parser.add_argument("--ld-chr-blocks", action="store_true",
                         help="With a .bed LD source: one LD block per run of equal chromosome code in the run's marker order (instead of --ld-block-size / --ld-blocks)")
+    parser.add_argument("--ld-form", choices=["stored", "factor"], default="stored",
+                        help="With .bed LD sources: stored (the default) forms and stores each LD block R_b; factor keeps the block's 2-bit genotype rows on the device and applies R_b p as G_b (G_b^T p) in every LD pass: exactly positive semi-definite, about 2 bits per genotype instead of 4 bytes per pair of markers, no window needed for a chromosome-sized block; takes no window, taper, --ld-precision f32 or --ld-packing off")
     parser.add_argument("--ld-packing", choices=["on", "off"], default="on",
                         help="Packed storage of symmetric LD blocks (on, the default) or full dense squares (off)")
     return parser
@@ -176,6 +183,28 @@ def check_bed_flags(parser, args):
             parser.error("--ld-taper stores packed bands: it cannot be combined with --ld-packing off")
 
 
+def check_ld_form(parser, args):
+    """--ld-form factor: every LD source a .bed, no stored-form option with it."""
+    if args.ld_form != "factor":
+        return
+    paths = (args.ld_files or "").split(",")
+    other = [p for p in paths if not p.endswith(".bed")]
+    if other:
+        parser.error("--ld-form factor needs a .bed LD source for every cohort: %s is not one"
+                     % other[0])
+    for flag, given in (("--ld-window", args.ld_window is not None),
+                        ("--ld-window-kb", args.ld_window_kb is not None),
+                        ("--ld-window-cm", args.ld_window_cm is not None),
+                        ("--ld-taper", args.ld_taper != "none")):
+        if given:
+            parser.error("--ld-form factor applies each LD block whole: it cannot be combined "
+                         "with %s" % flag)
+    if args.ld_precision == "f32":
+        parser.error("--ld-form factor stores no R: it cannot be combined with --ld-precision f32")
+    if args.ld_packing == "off":
+        parser.error("--ld-form factor stores no R: it cannot be combined with --ld-packing off")
+
+
 def pip_threshold_arg(text):
     """argparse type of --pip-threshold: a float in [0, 1]."""
     try:
@@ -188,6 +217,7 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_bed_flags(parser, args)
+    check_ld_form(parser, args)
     if argv is None:            # command line: --gpus N starts the ranks (before any GPU call)
         from launch import relaunch
 
@@ -306,7 +336,7 @@ def main(argv=None):
                         window=None if args.ld_window is None else int(args.ld_window),
                         window_kb=None if args.ld_window_kb is None else float(args.ld_window_kb),
                         window_cm=None if args.ld_window_cm is None else float(args.ld_window_cm),
-                        taper=args.ld_taper, chr_blocks=args.ld_chr_blocks)
+                        taper=args.ld_taper, chr_blocks=args.ld_chr_blocks, form=args.ld_form)
                 else:
                     by_path[p] = load_ld(p, s)
             lds.append(by_path[p])
@@ -319,6 +349,9 @@ def main(argv=None):
     # main.py:262-263 (the LD is uploaded per rank: its blocks of the partition)
     logging.info(f"Rank {rank} loaded R matrix with shape {(lds[0].M, lds[0].M)}\n")
     logging.debug(f"Rank {rank}: Loading R matrix took {time.time() - ts} seconds \n")
+    if rank == 0 and args.ld_form == "factor":
+        logging.info("LD form: factor (each pass applies G (G^T p) from the 2-bit genotype rows; "
+                     "no R is stored)\n")
 
     x0 = None
     if true_signal_fpath is not None:

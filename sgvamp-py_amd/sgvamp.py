@@ -522,6 +522,12 @@ class VAMP:
         if any(getattr(L, "uses_geno", False) for L in uniq):
             eng.geno_clear()   # the blocks are stored: the staged genotype rows can go
         eng.update_cg_exact()   # the run's CG column sets from the bytes stored (collective)
+        if any(getattr(L, "form", "stored") == "factor" for L in uniq):
+            # a factor matrix holds its genotype rows, not R: small, so the global
+            # bytes above put the run in the look-ahead CG mode on every rank count
+            held = sum(eng.stored_bytes(l) for l in range(len(uniq)))
+            logging.info("Rank %d: LD form factor, %.3f MB of genotype rows and tables held for "
+                         "%d LD matrix/matrices\n" % (self.rank, held / 1e6, len(uniq)))
         rr = np.asarray(r, dtype=np.float64)
         rr = rr.reshape(K, -1) if rr.size == K * self.M else rr
         for k in range(K):
