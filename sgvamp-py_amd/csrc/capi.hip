@@ -708,21 +708,15 @@ extern "C" int sgv_geno_clear(sgv_ctx* c) {
   return SGV_OK;
 }
 
-extern "C" int sgv_geno_set_block(sgv_ctx* c, int b, const uint8_t* rows, int64_t row_bytes,
-                                  int nsamp, int64_t* counts_out) {
-  ENTER(c);
-  if (b < 0 || b >= c->nblk || !rows || !counts_out || nsamp < 1 ||
-      row_bytes < ((int64_t)nsamp + 3) / 4)
-    return fail(c, SGV_ERR_ARG, "sgv_geno_set_block: bad arguments (block %d, %d samples, rows of "
-                "%lld bytes)", b, nsamp, (long long)row_bytes);
-  const int64_t n = c->bn[b];
+// n rows of .bed codes -> gb (empty on entry): rows, tables and nbad on the device,
+// the code counts in counts_out.  hs_later: the largest use of the pinned staging
+// buffer that follows in the same entry, so one sizing covers it.
+static int geno_stage(sgv_ctx* c, GenoBlock& gb, const uint8_t* rows, int64_t row_bytes, int nsamp,
+                      int64_t n, size_t hs_later, int64_t* counts_out) {
   const int64_t used = ((int64_t)nsamp + 3) / 4;
   const int64_t stride_w = ((int64_t)nsamp + 15) / 16;
   const size_t bits_bytes = (size_t)n * stride_w * 4;
   const size_t cnt_bytes = sizeof(long long) * 4 * (size_t)n;
-  if (c->geno.empty()) c->geno.resize(c->nblk);
-  GenoBlock& gb = c->geno[b];
-  geno_free(gb);
   HIPCHK(hipMalloc(&gb.d_bits, bits_bytes));
   HIPCHK(hipMalloc(&gb.d_lut, sizeof(double) * 4 * n));
   HIPCHK(hipMalloc(&gb.d_msd, sizeof(double) * 2 * n));
@@ -730,7 +724,7 @@ extern "C" int sgv_geno_set_block(sgv_ctx* c, int b, const uint8_t* rows, int64_
   gb.nsamp = nsamp;
   // rows need not be word aligned in the file: repacked to whole words (zero
   // filled: padding the kernels mask) in the pinned staging buffer
-  CHK(ensure_hstage(c, std::max(bits_bytes, cnt_bytes)));
+  CHK(ensure_hstage(c, std::max(std::max(bits_bytes, cnt_bytes), hs_later)));
   CHK(ensure_stage(c, cnt_bytes));
   uint8_t* hs = static_cast<uint8_t*>(c->h_stage);
   std::memset(hs, 0, bits_bytes);
@@ -753,6 +747,18 @@ extern "C" int sgv_geno_set_block(sgv_ctx* c, int b, const uint8_t* rows, int64_
   return SGV_OK;
 }
 
+extern "C" int sgv_geno_set_block(sgv_ctx* c, int b, const uint8_t* rows, int64_t row_bytes,
+                                  int nsamp, int64_t* counts_out) {
+  ENTER(c);
+  if (b < 0 || b >= c->nblk || !rows || !counts_out || nsamp < 1 ||
+      row_bytes < ((int64_t)nsamp + 3) / 4)
+    return fail(c, SGV_ERR_ARG, "sgv_geno_set_block: bad arguments (block %d, %d samples, rows of "
+                "%lld bytes)", b, nsamp, (long long)row_bytes);
+  if (c->geno.empty()) c->geno.resize(c->nblk);
+  geno_free(c->geno[b]);
+  return geno_stage(c, c->geno[b], rows, row_bytes, nsamp, c->bn[b], 0, counts_out);
+}
+
 // every owned block holds usable genotypes of nsamp samples (nsamp < 0: any, returned)
 static int geno_ready(sgv_ctx* c, const char* who, int* nsamp_io) {
   if ((int)c->geno.size() != c->nblk)
@@ -771,16 +777,31 @@ static int geno_ready(sgv_ctx* c, const char* who, int* nsamp_io) {
   return SGV_OK;
 }
 
+// block b can feed an LD build: it holds genotypes (how: where they come from) and
+// every marker has LD; band: packing is on and the block is formed in one piece.
+// Every refusal comes before any storage changes: the block stays as it was.
+static int geno_usable(sgv_ctx* c, const char* who, int b, bool band,
+                       const char* how = "sgv_geno_set_block") {
+  if (band && !c->packing)
+    return fail(c, SGV_ERR_STATE, "%s: a band is a packed layout and packing is off "
+                "(sgv_set_ld_packing)", who);
+  if ((int)c->geno.size() != c->nblk || !c->geno[b].d_bits)
+    return fail(c, SGV_ERR_STATE, "%s: block %d has no genotypes (%s)", who, b, how);
+  if (c->geno[b].nbad)
+    return fail(c, SGV_ERR_STATE, "%s: block %d has %lld marker(s) without LD (monomorphic or "
+                "unobserved)", who, b, (long long)c->geno[b].nbad);
+  if (band && c->bn[b] > (int64_t)65535 * 64)
+    return fail(c, SGV_ERR_ARG, "%s: block %d has %lld markers, at most %lld are formed in one "
+                "piece", who, b, (long long)c->bn[b], (long long)65535 * 64);
+  return SGV_OK;
+}
+
 extern "C" int sgv_geno_ld(sgv_ctx* c, int ld, int b) {
   ENTER(c);
   if (ld < 0 || ld >= c->nld || b < 0 || b >= c->nblk)
     return fail(c, SGV_ERR_ARG, "sgv_geno_ld: bad arguments (ld %d, block %d)", ld, b);
-  if ((int)c->geno.size() != c->nblk || !c->geno[b].d_bits)
-    return fail(c, SGV_ERR_STATE, "sgv_geno_ld: block %d has no genotypes (sgv_geno_set_block)", b);
+  CHK(geno_usable(c, "sgv_geno_ld", b, false));
   const GenoBlock& gb = c->geno[b];
-  if (gb.nbad)   // before any storage changes: the block stays as it was
-    return fail(c, SGV_ERR_STATE, "sgv_geno_ld: block %d has %lld marker(s) without LD "
-                "(monomorphic or unobserved)", b, (long long)gb.nbad);
   CHK(ld_alloc(c, ld, b, c->packing));    // R = G G^T is exactly symmetric
   const LdBlock& lb = c->ldb[ld][b];
   HIPCHK(launch_bed_syrk(gb.d_bits, gb.stride_w, gb.d_lut, (int)c->bn[b], gb.nsamp, lb.ptr,
@@ -797,13 +818,9 @@ extern "C" int sgv_geno_ld_factor(sgv_ctx* c, int ld, int b) {
   ENTER(c);
   if (ld < 0 || ld >= c->nld || b < 0 || b >= c->nblk)
     return fail(c, SGV_ERR_ARG, "sgv_geno_ld_factor: bad arguments (ld %d, block %d)", ld, b);
-  if ((int)c->geno.size() != c->nblk || !c->geno[b].d_bits)
-    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_factor: block %d has no genotypes "
-                "(sgv_geno_set_block; an earlier sgv_geno_ld_factor took them over)", b);
+  CHK(geno_usable(c, "sgv_geno_ld_factor", b, false,
+                  "sgv_geno_set_block; an earlier sgv_geno_ld_factor took them over"));
   GenoBlock& gb = c->geno[b];
-  if (gb.nbad)
-    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_factor: block %d has %lld marker(s) without LD "
-                "(monomorphic or unobserved)", b, (long long)gb.nbad);
   for (int o = 0; o < c->nblk; ++o)
     if (c->ldb[ld][o].ptr && c->ldb[ld][o].fmt != 3)
       return fail(c, SGV_ERR_STATE, "sgv_geno_ld_factor: LD matrix %d holds a stored block "
@@ -833,9 +850,26 @@ extern "C" int sgv_geno_ld_factor(sgv_ctx* c, int ld, int b) {
   return SGV_OK;
 }
 
-// windowed R_b: a packed band (or, where the band is as wide as the triangle, the
-// packed triangle) by sgv_set_ld_block_csr's allocation rule, zeroed, then the
-// in-window entries from the bits
+// windowed R_b of band width bw: a packed band (or, where the band is as wide as
+// the triangle, the packed triangle) by sgv_set_ld_block_csr's allocation rule,
+// zeroed, then the kept entries from the bits by launch(lb, ext)
+template <class Launch>
+static int geno_band_build(sgv_ctx* c, int ld, int b, int64_t bw, Launch launch) {
+  const int64_t n = c->bn[b];
+  int64_t ext = round_up(SYM_H + bw, BAND_Q);
+  if (ext >= n) ext = 0;   // the band is as wide as the triangle
+  CHK(ld_alloc(c, ld, b, 1, ext));
+  const LdBlock& lb = c->ldb[ld][b];
+  // a block kept from an earlier call of the same shape may hold a wider band
+  const int64_t g1 = (int64_t)lb.poff.size() - 1;
+  const size_t elems = (size_t)(lb.poff[g1] + (n - g1 * SYM_H) * lb.pw[g1]);
+  HIPCHK(hipMemsetAsync(lb.ptr, 0, lb.esz() * elems, c->st));
+  HIPCHK(launch(lb, ext));
+  CHK(stream_wait(c));
+  std::fill(c->rx0_valid.begin(), c->rx0_valid.end(), 0);
+  return SGV_OK;
+}
+
 extern "C" int sgv_geno_ld_band(sgv_ctx* c, int ld, int b, int64_t window) {
   ENTER(c);
   if (ld < 0 || ld >= c->nld || b < 0 || b >= c->nblk)
@@ -843,105 +877,82 @@ extern "C" int sgv_geno_ld_band(sgv_ctx* c, int ld, int b, int64_t window) {
   if (window < 1)
     return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band: window %lld (must be >= 1 marker)",
                 (long long)window);
-  if (!c->packing)
-    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band: a band is a packed layout and packing is off "
-                "(sgv_set_ld_packing)");
-  if ((int)c->geno.size() != c->nblk || !c->geno[b].d_bits)
-    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band: block %d has no genotypes "
-                "(sgv_geno_set_block)", b);
+  CHK(geno_usable(c, "sgv_geno_ld_band", b, true));
   const GenoBlock& gb = c->geno[b];
-  if (gb.nbad)   // before any storage changes: the block stays as it was
-    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band: block %d has %lld marker(s) without LD "
-                "(monomorphic or unobserved)", b, (long long)gb.nbad);
-  const int64_t n = c->bn[b];
-  if (n > (int64_t)65535 * 64)
-    return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band: block %d has %lld markers, at most %lld are "
-                "formed in one piece", b, (long long)n, (long long)65535 * 64);
-  const int64_t bw = std::min<int64_t>(window, n - 1);
-  int64_t ext = round_up(SYM_H + bw, BAND_Q);
-  if (ext >= n) ext = 0;   // the band is as wide as the triangle
-  CHK(ld_alloc(c, ld, b, 1, ext));
-  const LdBlock& lb = c->ldb[ld][b];
-  // a block kept from an earlier call of the same shape may hold a wider window
-  const int64_t g1 = (int64_t)lb.poff.size() - 1;
-  const size_t elems = (size_t)(lb.poff[g1] + (n - g1 * SYM_H) * lb.pw[g1]);
-  HIPCHK(hipMemsetAsync(lb.ptr, 0, lb.esz() * elems, c->st));
-  HIPCHK(launch_bed_syrk_band(gb.d_bits, gb.stride_w, gb.d_lut, (int)n, gb.nsamp, bw, ext, lb.ptr,
-                              lb.d_poff, lb.d_pw, lb.bits, c->st));
-  CHK(stream_wait(c));
-  std::fill(c->rx0_valid.begin(), c->rx0_valid.end(), 0);
+  const int64_t n = c->bn[b], bw = std::min<int64_t>(window, n - 1);
+  return geno_band_build(c, ld, b, bw, [&](const LdBlock& lb, int64_t ext) {
+    return launch_bed_band(gb.d_bits, gb.stride_w, gb.d_lut, (int)n, gb.nsamp, bw, nullptr, nullptr,
+                           nullptr, 0.0, ext, lb.ptr, lb.d_poff, lb.d_pw, lb.bits, c->st);
+  });
+}
+
+// the halo of a coupling on the device (its rows and tables, and C), freed on every
+// way out
+struct HaloGuard {
+  GenoBlock g;
+  double* d_C = nullptr;
+  ~HaloGuard() {
+    geno_free(g);
+    if (d_C) (void)hipFree(d_C);
+  }
+};
+
+static int geno_coupling_ids(sgv_ctx* c, const char* who, int ld, int gb, int nr, int nc) {
+  if (ld < 0 || ld >= c->nld || gb < 0 || gb + 1 >= c->nblk_global || nr < 1 || nc < 1)
+    return fail(c, SGV_ERR_ARG, "%s: bad arguments (ld %d, gb %d, %d x %d)", who, ld, gb, nr, nc);
   return SGV_OK;
 }
 
-// coupling gb from the halo's rows: staged, counted and tabulated as a block's,
-// C formed on the device, downloaded and registered as sgv_set_ld_coupling's
+// coupling gb from the halo's rows (after geno_coupling_ids): a rank that owns
+// neither piece only records its shape; else the rows are staged, counted and
+// tabulated as a block's, C (zeroed) is formed on the device by launch(halo),
+// downloaded and registered as sgv_set_ld_coupling's.  ptrs_ok: the entry's own
+// pointers are given; check(): its other argument checks, after the common ones;
+// hs_later: its own use of the pinned staging buffer.
+template <class Check, class Launch>
+static int geno_coupling_build(sgv_ctx* c, const char* who, int ld, int gb, int nr, int nc,
+                               const uint8_t* rows, int64_t row_bytes, int nsamp, bool ptrs_ok,
+                               size_t hs_later, int64_t* counts_out, Check check, Launch launch) {
+  const int ba = gb - c->blk0, bb = gb + 1 - c->blk0;
+  const bool own = (ba >= 0 && ba < c->nblk) || (bb >= 0 && bb < c->nblk);
+  if (!own) return ld_set_coupling(c, who, ld, gb, nr, nc, nullptr);
+  if (!rows || !counts_out || !ptrs_ok || nsamp < 1 || row_bytes < ((int64_t)nsamp + 3) / 4)
+    return fail(c, SGV_ERR_ARG, "%s: bad rows (coupling %d, %d samples, rows of %lld bytes)", who,
+                gb, nsamp, (long long)row_bytes);
+  if ((ba >= 0 && ba < c->nblk && nr > c->bn[ba]) || (bb >= 0 && bb < c->nblk && nc > c->bn[bb]))
+    return fail(c, SGV_ERR_ARG, "%s: %d x %d exceeds the pieces", who, nr, nc);
+  CHK(check());
+  const size_t c_bytes = sizeof(double) * (size_t)nr * nc;
+  HaloGuard halo;
+  HIPCHK(hipMalloc(&halo.d_C, c_bytes));
+  CHK(geno_stage(c, halo.g, rows, row_bytes, nsamp, (int64_t)nr + nc, std::max(c_bytes, hs_later),
+                 counts_out));
+  if (halo.g.nbad)   // nothing registered: the coupling stays as it was
+    return fail(c, SGV_ERR_STATE, "%s: coupling %d has %lld marker(s) without LD (monomorphic or "
+                "unobserved)", who, gb, (long long)halo.g.nbad);
+  HIPCHK(hipMemsetAsync(halo.d_C, 0, c_bytes, c->st));
+  CHK(launch(halo));
+  HIPCHK(hipMemcpyAsync(c->h_stage, halo.d_C, c_bytes, hipMemcpyDeviceToHost, c->st));
+  CHK(stream_wait(c));
+  return ld_set_coupling(c, who, ld, gb, nr, nc, static_cast<const double*>(c->h_stage));
+}
+
 extern "C" int sgv_geno_coupling(sgv_ctx* c, int ld, int gb, int nr, int nc, const uint8_t* rows,
                                  int64_t row_bytes, int nsamp, int64_t window,
                                  int64_t* counts_out) {
   ENTER(c);
-  if (ld < 0 || ld >= c->nld || gb < 0 || gb + 1 >= c->nblk_global || nr < 1 || nc < 1)
-    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling: bad arguments (ld %d, gb %d, %d x %d)", ld, gb,
-                nr, nc);
+  CHK(geno_coupling_ids(c, "sgv_geno_coupling", ld, gb, nr, nc));
   if (window < 1)
     return fail(c, SGV_ERR_ARG, "sgv_geno_coupling: window %lld (must be >= 1 marker)",
                 (long long)window);
-  const int ba = gb - c->blk0, bb = gb + 1 - c->blk0;
-  const bool own = (ba >= 0 && ba < c->nblk) || (bb >= 0 && bb < c->nblk);
-  if (!own) return ld_set_coupling(c, "sgv_geno_coupling", ld, gb, nr, nc, nullptr);
-  if (!rows || !counts_out || nsamp < 1 || row_bytes < ((int64_t)nsamp + 3) / 4)
-    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling: bad rows (coupling %d, %d samples, rows of "
-                "%lld bytes)", gb, nsamp, (long long)row_bytes);
-  if ((ba >= 0 && ba < c->nblk && nr > c->bn[ba]) || (bb >= 0 && bb < c->nblk && nc > c->bn[bb]))
-    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling: %d x %d exceeds the pieces", nr, nc);
-  const int64_t n = (int64_t)nr + nc;
-  const int64_t used = ((int64_t)nsamp + 3) / 4;
-  const int64_t stride_w = ((int64_t)nsamp + 15) / 16;
-  const size_t bits_bytes = (size_t)n * stride_w * 4;
-  const size_t cnt_bytes = sizeof(long long) * 4 * (size_t)n;
-  const size_t c_bytes = sizeof(double) * (size_t)nr * nc;
-  GenoBlock h;       // the halo's rows and tables, freed on every way out
-  struct Guard {
-    GenoBlock& g;
-    double* d_C = nullptr;
-    ~Guard() {
-      geno_free(g);
-      if (d_C) (void)hipFree(d_C);
-    }
-  } guard{h};
-  HIPCHK(hipMalloc(&h.d_bits, bits_bytes));
-  HIPCHK(hipMalloc(&h.d_lut, sizeof(double) * 4 * n));
-  HIPCHK(hipMalloc(&h.d_msd, sizeof(double) * 2 * n));
-  HIPCHK(hipMalloc(&guard.d_C, c_bytes));
-  CHK(ensure_hstage(c, std::max(std::max(bits_bytes, cnt_bytes), c_bytes)));
-  CHK(ensure_stage(c, cnt_bytes));
-  uint8_t* hs = static_cast<uint8_t*>(c->h_stage);
-  std::memset(hs, 0, bits_bytes);
-  for (int64_t i = 0; i < n; ++i)
-    std::memcpy(hs + (size_t)i * stride_w * 4, rows + (size_t)i * row_bytes, (size_t)used);
-  HIPCHK(hipMemcpyAsync(h.d_bits, hs, bits_bytes, hipMemcpyHostToDevice, c->st));
-  long long* d_cnt = static_cast<long long*>(c->d_stage);
-  HIPCHK(launch_bed_stats(h.d_bits, stride_w, (int)n, nsamp, d_cnt, h.d_lut, h.d_msd, c->st));
-  CHK(stream_wait(c));   // the bits have left the staging buffer
-  HIPCHK(hipMemcpyAsync(c->h_stage, d_cnt, cnt_bytes, hipMemcpyDeviceToHost, c->st));
-  CHK(stream_wait(c));
-  const long long* hc = static_cast<const long long*>(c->h_stage);
-  int64_t nbad = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    const long long c0 = hc[4 * i], c2 = hc[4 * i + 2], c3 = hc[4 * i + 3];
-    const long long nobs = c0 + c2 + c3, S1 = 2 * c0 + c2, S2 = 4 * c0 + c2;
-    if (nobs == 0 || nobs * S2 - S1 * S1 == 0) ++nbad;
-    for (int k = 0; k < 4; ++k) counts_out[4 * i + k] = (int64_t)hc[4 * i + k];
-  }
-  if (nbad)   // nothing registered: the coupling stays as it was
-    return fail(c, SGV_ERR_STATE, "sgv_geno_coupling: coupling %d has %lld marker(s) without LD "
-                "(monomorphic or unobserved)", gb, (long long)nbad);
-  HIPCHK(hipMemsetAsync(guard.d_C, 0, c_bytes, c->st));
-  HIPCHK(launch_bed_cross(h.d_bits, stride_w, h.d_lut, nr, nc, nsamp, window, c->ld_bits,
-                          guard.d_C, c->st));
-  HIPCHK(hipMemcpyAsync(c->h_stage, guard.d_C, c_bytes, hipMemcpyDeviceToHost, c->st));
-  CHK(stream_wait(c));
-  return ld_set_coupling(c, "sgv_geno_coupling", ld, gb, nr, nc,
-                         static_cast<const double*>(c->h_stage));
+  return geno_coupling_build(
+      c, "sgv_geno_coupling", ld, gb, nr, nc, rows, row_bytes, nsamp, true, 0, counts_out,
+      [] { return SGV_OK; },
+      [&](const HaloGuard& h) -> int {
+        HIPCHK(launch_bed_corner(h.g.d_bits, h.g.stride_w, h.g.d_lut, nr, nc, nsamp, window, nullptr,
+                                 0, nullptr, 0.0, c->ld_bits, h.d_C, c->st));
+        return SGV_OK;
+      });
 }
 
 // ---------------------------------------------------------------------------
@@ -990,8 +1001,7 @@ static int reach_aux_upload(sgv_ctx* c, ReachAux& x, const int32_t* reach, int64
   return SGV_OK;
 }
 
-// R_b with a reach per row: sgv_geno_ld_band's storage rule at bw = max (hi[i] - i),
-// zeroed, then the kept entries from the bits
+// R_b with a reach per row: sgv_geno_ld_band's storage rule at bw = max (hi[i] - i)
 extern "C" int sgv_geno_ld_band_reach(sgv_ctx* c, int ld, int b, const int32_t* hi,
                                       const double* pos, double span) {
   ENTER(c);
@@ -1016,35 +1026,15 @@ extern "C" int sgv_geno_ld_band_reach(sgv_ctx* c, int ld, int b, const int32_t* 
         return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band_reach: block %d: the reach of marker %lld "
                     "(to %d) is farther than the span %g: the taper's weight would be negative", b,
                     (long long)i, (int)hi[i], span);
-  if (!c->packing)
-    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band_reach: a band is a packed layout and packing "
-                "is off (sgv_set_ld_packing)");
-  if ((int)c->geno.size() != c->nblk || !c->geno[b].d_bits)
-    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band_reach: block %d has no genotypes "
-                "(sgv_geno_set_block)", b);
+  CHK(geno_usable(c, "sgv_geno_ld_band_reach", b, true));
   const GenoBlock& gb = c->geno[b];
-  if (gb.nbad)   // before any storage changes: the block stays as it was
-    return fail(c, SGV_ERR_STATE, "sgv_geno_ld_band_reach: block %d has %lld marker(s) without LD "
-                "(monomorphic or unobserved)", b, (long long)gb.nbad);
-  if (n > (int64_t)65535 * 64)
-    return fail(c, SGV_ERR_ARG, "sgv_geno_ld_band_reach: block %d has %lld markers, at most %lld "
-                "are formed in one piece", b, (long long)n, (long long)65535 * 64);
   ReachAux aux;
   CHK(ensure_hstage(c, reach_aux_bytes(n, n, pos != nullptr)));
   CHK(reach_aux_upload(c, aux, hi, n, pos, n));
-  int64_t ext = round_up(SYM_H + bw, BAND_Q);
-  if (ext >= n) ext = 0;   // the band is as wide as the triangle
-  CHK(ld_alloc(c, ld, b, 1, ext));
-  const LdBlock& lb = c->ldb[ld][b];
-  // a block kept from an earlier call of the same shape may hold a wider reach
-  const int64_t g1 = (int64_t)lb.poff.size() - 1;
-  const size_t elems = (size_t)(lb.poff[g1] + (n - g1 * SYM_H) * lb.pw[g1]);
-  HIPCHK(hipMemsetAsync(lb.ptr, 0, lb.esz() * elems, c->st));
-  HIPCHK(launch_bed_syrk_reach(gb.d_bits, gb.stride_w, gb.d_lut, (int)n, gb.nsamp, hi, aux.d_reach,
-                               aux.d_pos, span, ext, lb.ptr, lb.d_poff, lb.d_pw, lb.bits, c->st));
-  CHK(stream_wait(c));
-  std::fill(c->rx0_valid.begin(), c->rx0_valid.end(), 0);
-  return SGV_OK;
+  return geno_band_build(c, ld, b, bw, [&](const LdBlock& lb, int64_t ext) {
+    return launch_bed_band(gb.d_bits, gb.stride_w, gb.d_lut, (int)n, gb.nsamp, 0, hi, aux.d_reach,
+                           aux.d_pos, span, ext, lb.ptr, lb.d_poff, lb.d_pw, lb.bits, c->st);
+  });
 }
 
 // sgv_geno_coupling with a count of kept head columns per tail row
@@ -1053,88 +1043,39 @@ extern "C" int sgv_geno_coupling_reach(sgv_ctx* c, int ld, int gb, int nr, int n
                                        const int32_t* keep, const double* pos, double span,
                                        int64_t* counts_out) {
   ENTER(c);
-  if (ld < 0 || ld >= c->nld || gb < 0 || gb + 1 >= c->nblk_global || nr < 1 || nc < 1)
-    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: bad arguments (ld %d, gb %d, %d x %d)",
-                ld, gb, nr, nc);
-  const int ba = gb - c->blk0, bb = gb + 1 - c->blk0;
-  const bool own = (ba >= 0 && ba < c->nblk) || (bb >= 0 && bb < c->nblk);
-  if (!own) return ld_set_coupling(c, "sgv_geno_coupling_reach", ld, gb, nr, nc, nullptr);
-  if (!rows || !counts_out || !keep || nsamp < 1 || row_bytes < ((int64_t)nsamp + 3) / 4)
-    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: bad rows (coupling %d, %d samples, rows "
-                "of %lld bytes)", gb, nsamp, (long long)row_bytes);
-  if ((ba >= 0 && ba < c->nblk && nr > c->bn[ba]) || (bb >= 0 && bb < c->nblk && nc > c->bn[bb]))
-    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: %d x %d exceeds the pieces", nr, nc);
+  CHK(geno_coupling_ids(c, "sgv_geno_coupling_reach", ld, gb, nr, nc));
   const int64_t n = (int64_t)nr + nc;
   int kmax = 0;
-  for (int a = 0; a < nr; ++a) {
-    if (keep[a] < 0 || keep[a] > nc || (a && keep[a] < keep[a - 1]))
-      return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: keep[%d] = %d of coupling %d (must be "
-                  "in [0, %d] and non-decreasing)", a, (int)keep[a], gb, nc);
-    kmax = std::max<int>(kmax, keep[a]);
-  }
-  int64_t at;
-  if (const char* why = reach_pos_error(pos, n, span, &at))
-    return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: coupling %d: %s (span %g, halo row "
-                "%lld)", gb, why, span, (long long)at);
-  if (pos)
-    for (int a = 0; a < nr; ++a)
-      if (keep[a] > 0 && pos[nr + keep[a] - 1] - pos[a] > span)
-        return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: coupling %d: tail row %d keeps %d "
-                    "head column(s), farther than the span %g: the taper's weight would be "
-                    "negative", gb, a, (int)keep[a], span);
-  const int64_t used = ((int64_t)nsamp + 3) / 4;
-  const int64_t stride_w = ((int64_t)nsamp + 15) / 16;
-  const size_t bits_bytes = (size_t)n * stride_w * 4;
-  const size_t cnt_bytes = sizeof(long long) * 4 * (size_t)n;
-  const size_t c_bytes = sizeof(double) * (size_t)nr * nc;
-  GenoBlock h;       // the halo's rows and tables, freed on every way out
-  struct Guard {
-    GenoBlock& g;
-    double* d_C = nullptr;
-    ~Guard() {
-      geno_free(g);
-      if (d_C) (void)hipFree(d_C);
-    }
-  } guard{h};
   ReachAux aux;
-  HIPCHK(hipMalloc(&h.d_bits, bits_bytes));
-  HIPCHK(hipMalloc(&h.d_lut, sizeof(double) * 4 * n));
-  HIPCHK(hipMalloc(&h.d_msd, sizeof(double) * 2 * n));
-  HIPCHK(hipMalloc(&guard.d_C, c_bytes));
-  CHK(ensure_hstage(c, std::max(std::max(std::max(bits_bytes, cnt_bytes), c_bytes),
-                                reach_aux_bytes(nr, n, pos != nullptr))));
-  CHK(ensure_stage(c, cnt_bytes));
-  uint8_t* hs = static_cast<uint8_t*>(c->h_stage);
-  std::memset(hs, 0, bits_bytes);
-  for (int64_t i = 0; i < n; ++i)
-    std::memcpy(hs + (size_t)i * stride_w * 4, rows + (size_t)i * row_bytes, (size_t)used);
-  HIPCHK(hipMemcpyAsync(h.d_bits, hs, bits_bytes, hipMemcpyHostToDevice, c->st));
-  long long* d_cnt = static_cast<long long*>(c->d_stage);
-  HIPCHK(launch_bed_stats(h.d_bits, stride_w, (int)n, nsamp, d_cnt, h.d_lut, h.d_msd, c->st));
-  CHK(stream_wait(c));   // the bits have left the staging buffer
-  HIPCHK(hipMemcpyAsync(c->h_stage, d_cnt, cnt_bytes, hipMemcpyDeviceToHost, c->st));
-  CHK(stream_wait(c));
-  const long long* hc = static_cast<const long long*>(c->h_stage);
-  int64_t nbad = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    const long long c0 = hc[4 * i], c2 = hc[4 * i + 2], c3 = hc[4 * i + 3];
-    const long long nobs = c0 + c2 + c3, S1 = 2 * c0 + c2, S2 = 4 * c0 + c2;
-    if (nobs == 0 || nobs * S2 - S1 * S1 == 0) ++nbad;
-    for (int k = 0; k < 4; ++k) counts_out[4 * i + k] = (int64_t)hc[4 * i + k];
-  }
-  if (nbad)   // nothing registered: the coupling stays as it was
-    return fail(c, SGV_ERR_STATE, "sgv_geno_coupling_reach: coupling %d has %lld marker(s) "
-                "without LD (monomorphic or unobserved)", gb, (long long)nbad);
-  HIPCHK(hipMemsetAsync(guard.d_C, 0, c_bytes, c->st));
-  if (kmax > 0) {   // an all-zero keep: the zero coupling
-    CHK(reach_aux_upload(c, aux, keep, nr, pos, n));
-    HIPCHK(launch_bed_cross_reach(h.d_bits, stride_w, h.d_lut, nr, nc, nsamp, aux.d_reach, kmax,
-                                  aux.d_pos, span, c->ld_bits, guard.d_C, c->st));
-  }
-  HIPCHK(hipMemcpyAsync(c->h_stage, guard.d_C, c_bytes, hipMemcpyDeviceToHost, c->st));
-  CHK(stream_wait(c));
-  return ld_set_coupling(c, "sgv_geno_coupling_reach", ld, gb, nr, nc,
-                         static_cast<const double*>(c->h_stage));
+  return geno_coupling_build(
+      c, "sgv_geno_coupling_reach", ld, gb, nr, nc, rows, row_bytes, nsamp, keep != nullptr,
+      reach_aux_bytes(nr, n, pos != nullptr), counts_out,
+      [&]() -> int {
+        for (int a = 0; a < nr; ++a) {
+          if (keep[a] < 0 || keep[a] > nc || (a && keep[a] < keep[a - 1]))
+            return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: keep[%d] = %d of coupling %d "
+                        "(must be in [0, %d] and non-decreasing)", a, (int)keep[a], gb, nc);
+          kmax = std::max<int>(kmax, keep[a]);
+        }
+        int64_t at;
+        if (const char* why = reach_pos_error(pos, n, span, &at))
+          return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: coupling %d: %s (span %g, halo row "
+                      "%lld)", gb, why, span, (long long)at);
+        if (pos)
+          for (int a = 0; a < nr; ++a)
+            if (keep[a] > 0 && pos[nr + keep[a] - 1] - pos[a] > span)
+              return fail(c, SGV_ERR_ARG, "sgv_geno_coupling_reach: coupling %d: tail row %d keeps "
+                          "%d head column(s), farther than the span %g: the taper's weight would "
+                          "be negative", gb, a, (int)keep[a], span);
+        return SGV_OK;
+      },
+      [&](const HaloGuard& h) -> int {
+        if (kmax == 0) return SGV_OK;   // an all-zero keep: the zero coupling
+        CHK(reach_aux_upload(c, aux, keep, nr, pos, n));
+        HIPCHK(launch_bed_corner(h.g.d_bits, h.g.stride_w, h.g.d_lut, nr, nc, nsamp, 0, aux.d_reach,
+                                 kmax, aux.d_pos, span, c->ld_bits, h.d_C, c->st));
+        return SGV_OK;
+      });
 }
 
 extern "C" int sgv_geno_r(sgv_ctx* c, int k, const double* y) {

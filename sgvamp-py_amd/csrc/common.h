@@ -724,31 +724,23 @@ hipError_t launch_bed_stats(const uint32_t* d_bits, int64_t stride_w, int n, int
 hipError_t launch_bed_syrk(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int n,
                            int nsamp, void* d_R, int64_t lda, int packed, const int64_t* d_poff,
                            const int64_t* d_pw, int bits, hipStream_t st);
-// windowed R: only entries with |i - j| <= window, into a zeroed packed block of
-// stored extent ext (0: the packed triangle); entry for entry launch_bed_syrk's
-hipError_t launch_bed_syrk_band(const uint32_t* d_bits, int64_t stride_w, const double* d_lut,
-                                int n, int nsamp, int64_t window, int64_t ext, void* d_R,
-                                const int64_t* d_poff, const int64_t* d_pw, int bits,
-                                hipStream_t st);
+// windowed R into a zeroed packed block of stored extent ext (0: the packed
+// triangle), entry for entry launch_bed_syrk's.  hi == NULL: entries with |i - j| <=
+// window.  Else entries (i, j), i <= j <= hi[i] (hi: the host's copy of d_hi, checked
+// by the caller, sizes the grid), times 1 - (pos[j] - pos[i]) / span where d_pos is
+// given
+hipError_t launch_bed_band(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int n,
+                           int nsamp, int64_t window, const int32_t* hi, const int32_t* d_hi,
+                           const double* d_pos, double span, int64_t ext, void* d_R,
+                           const int64_t* d_poff, const int64_t* d_pw, int bits, hipStream_t st);
 // C = G_tail G_head^T (nr x nc doubles, zeroed by the caller) of nr + nc staged
-// rows, entries (a, c) with c + nr - a <= window; bits == 32: rounded once to f32
-hipError_t launch_bed_cross(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int nr,
-                            int nc, int nsamp, int64_t window, int bits, double* d_C,
-                            hipStream_t st);
-// distance-windowed R: entries (i, j), i <= j <= hi[i] (hi: the host's copy of d_hi,
-// checked by the caller, sizes the grid), times 1 - (pos[j] - pos[i]) / span where
-// d_pos is given; storage, zeroing and rounding as launch_bed_syrk_band's
-hipError_t launch_bed_syrk_reach(const uint32_t* d_bits, int64_t stride_w, const double* d_lut,
-                                 int n, int nsamp, const int32_t* hi, const int32_t* d_hi,
-                                 const double* d_pos, double span, int64_t ext, void* d_R,
-                                 const int64_t* d_poff, const int64_t* d_pw, int bits,
-                                 hipStream_t st);
-// launch_bed_cross with entries (a, c), c < keep[a] (kmax: the largest, >= 1), times
+// rows; bits == 32: rounded once to f32.  d_keep == NULL: entries (a, c) with c + nr
+// - a <= window.  Else entries with c < keep[a] (kmax: the largest, >= 1), times
 // 1 - (pos[nr + c] - pos[a]) / span where d_pos (nr + nc positions) is given
-hipError_t launch_bed_cross_reach(const uint32_t* d_bits, int64_t stride_w, const double* d_lut,
-                                  int nr, int nc, int nsamp, const int32_t* d_keep, int kmax,
-                                  const double* d_pos, double span, int bits, double* d_C,
-                                  hipStream_t st);
+hipError_t launch_bed_corner(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int nr,
+                             int nc, int nsamp, int64_t window, const int32_t* d_keep, int kmax,
+                             const double* d_pos, double span, int bits, double* d_C,
+                             hipStream_t st);
 hipError_t launch_bed_row_dot(const uint32_t* d_bits, int64_t stride_w, const double* d_lut, int n,
                               int nsamp, const double* d_y, double* d_out, hipStream_t st);
 hipError_t launch_bed_g_accum(const uint32_t* d_bits, int64_t stride_w, const double* d_msd, int n,

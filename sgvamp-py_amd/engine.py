@@ -271,6 +271,13 @@ class Engine:
         on every rank for every coupling.  Returns the rows' (nr + nc, 4) code
         counts, or None.  check(counts), if given, runs before the library's error
         for rows without LD is raised, so the caller can name them."""
+        return self._geno_coupling("sgv_geno_coupling", ld, gb, nr, nc, rows, nsamp,
+                                   lambda own, n: (int(window),), check)
+
+    def _geno_coupling(self, entry, ld, gb, nr, nc, rows, nsamp, own_args, check):
+        """The two genotype couplings: the halo rows are read and validated only
+        where this rank owns one of the two pieces; own_args(own, n) gives the
+        entry's own arguments (between nsamp and the counts)."""
         own = self.b0 <= gb < self.b1 or self.b0 <= gb + 1 < self.b1
         n = int(nr) + int(nc)
         counts, rp, cp, nb = None, None, None, 0
@@ -284,11 +291,12 @@ class Engine:
             counts = np.zeros((n, 4), dtype=np.int64)
             rp, cp, nb = rows.ctypes.data_as(hb._c_u8_p), counts.ctypes.data_as(hb._c_i64_p), \
                 int(rows.shape[1])
-        rc = self.ctx.lib.sgv_geno_coupling(self.ctx.h, int(ld), int(gb), int(nr), int(nc), rp, nb,
-                                            int(nsamp), int(window), cp)
+        args = own_args(own, n)
+        rc = getattr(self.ctx.lib, entry)(self.ctx.h, int(ld), int(gb), int(nr), int(nc), rp, nb,
+                                          int(nsamp), *args, cp)
         if rc != hb.SGV_OK and check is not None and counts is not None:
             check(counts)
-        self.ctx.check(rc, "sgv_geno_coupling")
+        self.ctx.check(rc, entry)
         return counts
 
     def geno_ld_band_reach(self, ld, b_global, hi, pos=None, span=0.0):
@@ -317,34 +325,20 @@ class Engine:
         """geno_coupling with keep (nr counts of head columns: entry (a, c) is kept
         iff c < keep[a]) in place of the window and, for the taper, pos (the nr + nc
         halo rows' positions) and span.  Called on every rank for every coupling."""
-        own = self.b0 <= gb < self.b1 or self.b0 <= gb + 1 < self.b1
-        n = int(nr) + int(nc)
-        counts, rp, cp, kp, pp, nb = None, None, None, None, None, 0
-        if own:
-            rows = np.asarray(rows() if callable(rows) else rows)
-            if rows.dtype != np.uint8 or rows.ndim != 2 or rows.shape[0] != n \
-                    or rows.shape[1] < (int(nsamp) + 3) // 4 or int(nsamp) < 1:
-                raise ValueError("genotype rows of coupling %d: %s %s, expected uint8 (%d, >= %d)"
-                                 % (gb, rows.dtype, rows.shape, n, (int(nsamp) + 3) // 4))
-            rows = np.ascontiguousarray(rows)
-            keep = np.ascontiguousarray(keep, dtype=np.int32).ravel()
-            if len(keep) != int(nr) or (pos is not None and np.size(pos) != n):
+        def own_args(own, n):
+            if not own:
+                return None, None, float(span)
+            k = np.ascontiguousarray(keep, dtype=np.int32).ravel()
+            if len(k) != int(nr) or (pos is not None and np.size(pos) != n):
                 raise ValueError("coupling %d: %d kept-column counts for %d tail rows (positions: "
-                                 "%s for %d halo rows)" % (gb, len(keep), int(nr),
+                                 "%s for %d halo rows)" % (gb, len(k), int(nr),
                                                            "none" if pos is None else np.size(pos), n))
-            counts = np.zeros((n, 4), dtype=np.int64)
-            rp, cp, nb = rows.ctypes.data_as(hb._c_u8_p), counts.ctypes.data_as(hb._c_i64_p), \
-                int(rows.shape[1])
-            kp = keep.ctypes.data_as(hb._c_i32_p)
+            pp = None
             if pos is not None:
-                pos = np.ascontiguousarray(pos, dtype=np.float64).ravel()
-                pp = hb.dptr(pos)
-        rc = self.ctx.lib.sgv_geno_coupling_reach(self.ctx.h, int(ld), int(gb), int(nr), int(nc),
-                                                  rp, nb, int(nsamp), kp, pp, float(span), cp)
-        if rc != hb.SGV_OK and check is not None and counts is not None:
-            check(counts)
-        self.ctx.check(rc, "sgv_geno_coupling_reach")
-        return counts
+                pp = hb.dptr(np.ascontiguousarray(pos, dtype=np.float64).ravel())
+            return k.ctypes.data_as(hb._c_i32_p), pp, float(span)
+        return self._geno_coupling("sgv_geno_coupling_reach", ld, gb, nr, nc, rows, nsamp,
+                                   own_args, check)
 
     def geno_r(self, k, y):
         """r_k = G y over this rank's blocks (get_vector(VEC_R, k) reads it)."""

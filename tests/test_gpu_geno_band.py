@@ -1,5 +1,6 @@
-"""Windowed LD from .bed genotypes on the device (geno.hip: k_bed_syrk_band,
-k_bed_cross): packed bands and the couplings of band pieces, formed from the bits.
+"""Windowed LD from .bed genotypes on the device (geno.hip: k_bed_band, k_bed_corner
+with their window policies): packed bands and the couplings of band pieces, formed
+from the bits.
 
 The definition (include/sgvamp_hip.h, "windowed genotype LD"): R[i][j] = (G G^T)[i][j]
 where |i - j| <= W, exactly 0 elsewhere.  The band is required to equal the
@@ -234,12 +235,12 @@ def cut_prefix(tmp_path_factory):
                      *bed_ref.bim_fam(CUT_N, CUT_NS))
 
 
-def coupling_by_unit_vectors(eng, rows, cols):
+def coupling_by_unit_vectors(eng, rows, cols, M=CUT_N):
     """out[a][c] = (R e_{cols[c]})[rows[a]]: products with 1.0 and zeros, exact."""
     out = np.empty((len(rows), len(cols)))
     for c0 in range(0, len(cols), 16):
         cc = cols[c0:c0 + 16]
-        V = np.zeros((len(cc), CUT_N))
+        V = np.zeros((len(cc), M))
         V[np.arange(len(cc)), cc] = 1.0
         out[:, c0:c0 + len(cc)] = eng.ld_matvec(0, V)[:, rows].T
     return out
@@ -288,6 +289,70 @@ def test_pieces_and_coupling_are_the_uncut_band(cut_prefix, bits):
     finally:
         whole.close()
         cut.close()
+
+
+# ---- the corner: a marker window is a count of kept columns per row ----------------
+CORNER_PIECES, CORNER_NR, CORNER_NC = [200, 150], 130, 70
+
+
+@functools.lru_cache(maxsize=None)
+def corner_case(N):
+    """The 350 markers' codes and their uncut f64 geno_ld block, computed once."""
+    M = sum(CORNER_PIECES)
+    codes = bed_ref.draw_codes(M, N, miss=0.03, seed=4100 + N)
+    assert not bed_ref.unusable(codes).any()
+    eng = Engine([M], K=1)
+    try:
+        eng.geno_set_block(0, bed_ref.pack(codes), N)
+        eng.geno_ld(0, 0)
+        T = eng.get_ld_block(0, 0)
+    finally:
+        eng.close()
+    codes.setflags(write=False)
+    T.setflags(write=False)
+    return codes, T
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+@pytest.mark.parametrize("N", [5, 130])
+def test_window_corner_is_the_keep_corner(N, bits):
+    """geno_coupling(W) == geno_coupling_reach(keep[a] = clip(W - nr + a + 1, 0, nc)),
+    bit for bit, at nr = 130, nc = 70 (three row tiles, two column tiles, nr != nc):
+    W = 1 keeps one entry (rows above it keep 0), W = 150 keeps all nc columns from
+    row 49 on.  Both are the uncut block's corner where c + nr - a <= W (rounded
+    once through f32 for 32 bits) and exactly 0.0 elsewhere."""
+    nr, nc, (n0, n1) = CORNER_NR, CORNER_NC, CORNER_PIECES
+    codes, T = corner_case(N)
+    corner = T[n0 - nr:n0, n0:n0 + nc]
+    if bits == 32:
+        corner = f32(corner)
+    rows = bed_ref.pack(codes[n0 - nr:n0 + nc])
+    tail, head = np.arange(n0 - nr, n0), np.arange(n0, n0 + nc)
+    a, c = np.arange(nr)[:, None], np.arange(nc)[None, :]
+    A, B = Engine(CORNER_PIECES, K=1), Engine(CORNER_PIECES, K=1)
+    try:
+        for eng in (A, B):
+            eng.set_ld_precision(bits)
+            stage(eng, [codes[:n0], codes[n0:]])
+            for b in range(2):
+                eng.geno_ld(0, b)
+        for W in (1, 64, 150):
+            keep = np.clip(W - nr + np.arange(nr) + 1, 0, nc)
+            A.geno_coupling(0, 0, nr, nc, rows, N, W)
+            B.geno_coupling_reach(0, 0, nr, nc, rows, N, keep)
+            CA = coupling_by_unit_vectors(A, tail, head, n0 + n1)
+            CB = coupling_by_unit_vectors(B, tail, head, n0 + n1)
+            inside = c + nr - a <= W
+            assert inside.sum() == keep.sum()
+            assert (keep[-2], keep[-1], keep[48], keep[49]) == \
+                {1: (0, 1, 0, 0), 64: (63, 64, 0, 0), 150: (nc, nc, nc - 1, nc)}[W]
+            np.testing.assert_array_equal(CA, CB)
+            for C in (CA, CB):
+                np.testing.assert_array_equal(C, np.where(inside, corner, 0.0))
+                assert not C[~inside].any()
+    finally:
+        A.close()
+        B.close()
 
 
 # ---- refusals ------------------------------------------------------------------

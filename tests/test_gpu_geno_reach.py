@@ -1,5 +1,5 @@
-"""Distance-windowed LD from .bed genotypes on the device (geno.hip:
-k_bed_syrk_reach, k_bed_cross_reach): a reach per row instead of one window, and
+"""Distance-windowed LD from .bed genotypes on the device (geno.hip: k_bed_band,
+k_bed_corner with their row policies): a reach per row instead of one window, and
 the triangular taper that keeps the windowed block positive semi-definite.
 
 The definition (include/sgvamp_hip.h, "distance-windowed genotype LD"): for j >= i

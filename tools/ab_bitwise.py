@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Bitwise A/B of two builds: run fixed LD passes (packed VALU/MFMA, dense, the
-wide-item block sizes, band; the last two also f32-stored) and full VAMP runs of
-golden cases through the library at --lib, print one SHA-256 per result.  Two
-builds whose lines are equal produce the same bits (under the same SGV_AB
-switches: run it once per arm).
+wide-item block sizes, band; the last two also f32-stored), full VAMP runs of
+golden cases and every LD form built from .bed genotypes through the library at
+--lib, print one SHA-256 per result.  Two builds whose lines are equal produce the
+same bits (under the same SGV_AB switches: run it once per arm).
 
   python tools/ab_bitwise.py --lib sgvamp-py_amd/libsgvamp_hip.so > a.txt
   python tools/ab_bitwise.py --lib ab_lib/base.so > b.txt; diff a.txt b.txt"""
@@ -22,6 +22,69 @@ sys.path.insert(0, ROOT)
 
 def h(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16]
+
+
+def geno(Engine):
+    """Every LD form built from .bed genotypes (geno.hip), f64 and f32 stored: the
+    dense build, marker windows across the tile and panel edges, a ragged reach
+    without and with the taper, the corner by window and by kept columns (tests/
+    test_gpu_geno_band.py's shapes), r and g."""
+    import hip_backend as hb
+    from tests import bed_ref
+    sizes, N = [130, 257, 700], 130
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+    codes = bed_ref.draw_codes(sum(sizes), N, miss=0.03, seed=7)
+    rs = np.random.RandomState(11)
+    hi = [np.maximum.accumulate(np.minimum(np.arange(n) + 1 + np.arange(n) * 7 % 90, n - 1))
+          for n in sizes]
+    pos = [np.cumsum(rs.uniform(0.5, 3.0, n)) for n in sizes]
+    span = [1.25 * float(np.max(p[r] - p)) for p, r in zip(pos, hi)]
+    pieces, nr, nc = [200, 150], 130, 70
+    halo = bed_ref.pack(codes[pieces[0] - nr:pieces[0] + nc])
+    E = np.zeros((nc, sum(pieces)))              # the head's unit vectors read C's columns
+    E[np.arange(nc), pieces[0] + np.arange(nc)] = 1.0
+
+    def corner(eng):
+        return h(np.concatenate([eng.ld_matvec(0, E[c:c + 16])[:, pieces[0] - nr:pieces[0]]
+                                 for c in range(0, nc, 16)]))
+    for bits, tag in ((64, "f64"), (32, "f32")):
+        eng = Engine(sizes, K=1)
+        eng.set_ld_precision(bits)
+        for b in range(len(sizes)):
+            eng.geno_set_block(b, bed_ref.pack(codes[offs[b]:offs[b + 1]]), N)
+
+        def blocks(what):
+            print("geno %s %s %s" % (tag, what,
+                                     " ".join(h(eng.get_ld_block(0, b)) for b in range(len(sizes)))))
+        for b in range(len(sizes)):
+            eng.geno_ld(0, b)
+        blocks("ld")
+        for W in (1, 64, 300):
+            for b in range(len(sizes)):
+                eng.geno_ld_band(0, b, W)
+            blocks("band W=%d" % W)
+        for taper in (False, True):
+            for b in range(len(sizes)):
+                eng.geno_ld_band_reach(0, b, hi[b], pos[b] if taper else None,
+                                       span[b] if taper else 0.0)
+            blocks("reach taper=%d" % taper)
+        eng.geno_r(0, rs.normal(size=N))
+        print("geno %s r %s" % (tag, h(eng.get_vector(hb.VEC_R, 0))))
+        print("geno %s g %s" % (tag, h(eng.geno_g(rs.normal(size=sum(sizes)), N))))
+        eng.close()
+        eng = Engine(pieces, K=1)
+        eng.set_ld_precision(bits)
+        for b, (lo, up) in enumerate(((0, pieces[0]), (pieces[0], sum(pieces)))):
+            eng.geno_set_block(b, bed_ref.pack(codes[lo:up]), N)
+            eng.geno_ld(0, b)
+        for W in (1, 64, 150):
+            eng.geno_coupling(0, 0, nr, nc, halo, N, W)
+            cw = corner(eng)
+            eng.geno_coupling_reach(0, 0, nr, nc, halo, N,
+                                    np.clip(W - nr + np.arange(nr) + 1, 0, nc))
+            ck = corner(eng)
+            print("geno %s corner W=%d window %s keep %s" % (tag, W, cw, ck))
+        eng.close()
 
 
 def main():
@@ -121,6 +184,7 @@ def main():
                          update_prior_from=f["update_prior_from"])
             print("vamp %s %s" % (name, h(np.array(xh))))
             v.engine.close()
+    geno(Engine)
 
 
 if __name__ == "__main__":

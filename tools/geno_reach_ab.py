@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Build time of one band piece (n = 65,536 markers, N = 10,000 samples, W = 1,000)
-from .bed bits by the distance-windowed kernel against the marker-window kernel,
-on one device in alternating arms:
+from .bed bits by k_bed_band with the reach read per row against the same kernel
+with the marker window formed in registers, on one device in alternating arms:
 
-  A  geno_ld_band(W)                          k_bed_syrk_band, the reference arm
-  B  geno_ld_band_reach(hi = min(i + W, n-1))  k_bed_syrk_reach, the same entries
+  A  geno_ld_band(W)                          the window policy, the reference arm
+  B  geno_ld_band_reach(hi = min(i + W, n-1))  the row policy, the same entries
   C  B with the triangular taper (pos = the index, D = W + 1)
   R  a ragged reach of the same MAXIMUM W: gaps between positions swing from 1 to
      4 and back along the piece, so the reach runs from W down to about W / 4
