@@ -2,7 +2,8 @@
 // host side: error handling, the A/B switch gate, context lifetime, host <->
 // device staging (pinned copies, probe uploads), solver settings, vectors, the
 // device data generator's entry points, output copies, timers.  The other
-// parts: exchange.hip, ldplan.hip, solver.hip (ctx.h lists them).
+// parts: exchange.hip, ldplan.hip, cg.hip, prior.hip, solver.hip (ctx.h lists
+// them).
 #include "ctx.h"
 
 static thread_local std::string g_last_err;
@@ -57,43 +58,31 @@ int stream_wait(sgv_ctx* c){
   return SGV_OK;
 }
 
+// the elapsed times of a list's event pairs to add(ms, i), the events back to the pool
+template <class Add>
+static void resolve_pairs(sgv_ctx* c, std::vector<std::pair<hipEvent_t, hipEvent_t>>& list, Add add) {
+  for (size_t i = 0; i < list.size(); ++i) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, list[i].first, list[i].second) == hipSuccess) add(ms, i);
+    c->evpool.push_back(list[i].first);
+    c->evpool.push_back(list[i].second);
+  }
+  list.clear();
+}
+
 void resolve_timers(sgv_ctx* c){
-  for (size_t i = 0; i < c->pending.size(); ++i) {
-    const auto& pr = c->pending[i];
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
-      c->ld_ms += ms;
-      if (c->pending_wide[i]) c->ld_ms_wide += ms;
-    }
-    c->evpool.push_back(pr.first);
-    c->evpool.push_back(pr.second);
-  }
-  c->pending.clear();
-  c->pending_wide.clear();
-  for (auto& pr : c->xpending) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) c->xchg_ms += ms;
-    c->evpool.push_back(pr.first);
-    c->evpool.push_back(pr.second);
-  }
-  c->xpending.clear();
-  for (auto& pr : c->gpending) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) c->host_wait_ms += ms;
-    c->evpool.push_back(pr.first);
-    c->evpool.push_back(pr.second);
-  }
-  c->gpending.clear();
-  for (auto& pr : c->empending) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
-      c->em_ms += ms;
-      c->em_loops_timed += 1.0;
-    }
-    c->evpool.push_back(pr.first);
-    c->evpool.push_back(pr.second);
-  }
-  c->empending.clear();
+  PassLedger& led = c->ledger;
+  resolve_pairs(c, led.pending, [&](float ms, size_t i) {
+    led.ms += ms;
+    if (led.pending_wide[i]) led.ms_wide += ms;
+  });
+  led.pending_wide.clear();
+  resolve_pairs(c, c->xpending, [&](float ms, size_t) { c->xchg_ms += ms; });
+  resolve_pairs(c, c->gpending, [&](float ms, size_t) { c->host_wait_ms += ms; });
+  resolve_pairs(c, c->empending, [&](float ms, size_t) {
+    c->em_ms += ms;
+    c->em_loops_timed += 1.0;
+  });
 }
 
 int event_pair(sgv_ctx* c, hipEvent_t* e0, hipEvent_t* e1){
@@ -482,7 +471,7 @@ extern "C" void sgv_destroy(sgv_ctx* c) {
   if (c->ev_den) (void)hipEventDestroy(c->ev_den);
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
-  for (auto* v : {&c->pending, &c->xpending, &c->gpending, &c->empending})
+  for (auto* v : {&c->ledger.pending, &c->xpending, &c->gpending, &c->empending})
     for (auto& pr : *v) {
       (void)hipEventDestroy(pr.first);
       (void)hipEventDestroy(pr.second);
@@ -1209,24 +1198,12 @@ extern "C" int sgv_timers(sgv_ctx* c, double* dst, int cap, int reset) {
   if (cap < 0 || (cap > 0 && !dst)) return fail(c, SGV_ERR_ARG, "sgv_timers: bad buffer");
   CHK(stream_wait(c));
   resolve_timers(c);
-  {
-    double t6[SGV_TIMERS_N];
-    t6[0] = c->ld_ms;
-    t6[1] = c->ld_launches;
-    t6[2] = c->ld_bytes;
-    t6[3] = c->rhs_bytes;
-    t6[4] = c->dense_bytes;
-    t6[5] = c->aux_bytes;
-    t6[6] = c->ld_flops;
-    t6[7] = c->ld_flops_wide;
-    t6[8] = c->ld_ms_wide;
-    t6[9] = c->ld_launches_wide;
-    for (int i = 0; i < std::min(cap, SGV_TIMERS_N); ++i) dst[i] = t6[i];
-  }
-  if (reset) {
-    c->ld_ms = c->ld_launches = c->rhs_bytes = c->ld_bytes = c->dense_bytes = c->aux_bytes = 0.0;
-    c->ld_flops = c->ld_flops_wide = c->ld_ms_wide = c->ld_launches_wide = 0.0;
-  }
+  const PassLedger& led = c->ledger;
+  const double t[SGV_TIMERS_N] = {led.ms,          led.n.launches,  led.n.bytes, led.n.rhs_bytes,
+                                  led.n.dense_bytes, led.n.aux_bytes, led.n.flops, led.n.flops_wide,
+                                  led.ms_wide,     led.n.launches_wide};
+  for (int i = 0; i < std::min(cap, SGV_TIMERS_N); ++i) dst[i] = t[i];
+  if (reset) c->ledger.clear_counts();
   return SGV_OK;
 }
 

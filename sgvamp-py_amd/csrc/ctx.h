@@ -4,8 +4,10 @@
 // units share.  The units: capi.hip (lifetime, staging, vectors, generator,
 // timers), exchange.hip (the ordered cross-rank reductions, RCCL / host
 // exchange, the EM exchange model), ldplan.hip (LD storage, pass plans, the LD
-// pass), solver.hip (CG, LMMSE, denoiser, EM, MLE, the step driver).  Which kernel
-// form an LD pass takes is decided in one host-only unit, pass_form.cpp.
+// pass), cg.hip (the CG iteration, its two loops, the operator seam), prior.hip
+// (denoiser, posterior, EM, MLE), solver.hip (LMMSE, the step driver, the
+// worker).  Which kernel form an LD pass takes is decided in one host-only unit,
+// pass_form.cpp.
 #pragma once
 #include "common.h"
 #include "hybrd.h"
@@ -195,6 +197,42 @@ static inline int sym_class_nc(int cls) { return std::min(16, 2 << (cls + 1)); }
 static inline bool fused_ctl_pays(int nv, int nblk) {
   return nblk <= EM_CTL_MAXBLK && nv * nblk <= 128;
 }
+
+// The pass ledger: what ld_pass counts of every pass it enqueues -- the counters
+// of sgv_timers and the passes' event pairs still to be resolved into ld_ms
+// (resolve_timers).  A caller that may find its passes to have been no-ops (the
+// pipelined CG's look-ahead iteration) takes a mark() before them and rolls
+// back to it: every counter, and the event pairs added since, to `pool`.
+struct PassLedger {
+  struct Counts {
+    double launches = 0.0, bytes = 0.0, rhs_bytes = 0.0, dense_bytes = 0.0, aux_bytes = 0.0;
+    // algorithmic flops of the passes (2 per multiply-add: row part of every stored
+    // element, column part of the packed off-diagonal-block ones), and the 9..16-
+    // column passes' share (their bound is the f64 matrix core, not HBM)
+    double flops = 0.0, flops_wide = 0.0, launches_wide = 0.0;
+  } n;
+  double ms = 0.0, ms_wide = 0.0;   // resolved event times
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+  std::vector<int> pending_wide;   // the pass ran 9..16 columns (16x16x4 MFMA)
+  struct Mark {
+    Counts n;
+    size_t npending;
+  };
+  Mark mark() const { return {n, pending.size()}; }
+  void rollback(const Mark& m, std::vector<hipEvent_t>& pool) {
+    n = m.n;
+    while (pending.size() > m.npending) {
+      pool.push_back(pending.back().first);
+      pool.push_back(pending.back().second);
+      pending.pop_back();
+      pending_wide.pop_back();
+    }
+  }
+  void clear_counts() {
+    n = Counts{};
+    ms = ms_wide = 0.0;
+  }
+};
 
 struct sgv_ctx {
   int dev = 0;
@@ -393,8 +431,7 @@ struct sgv_ctx {
   hipEvent_t ev_den = nullptr;    // sgv_step: the denoiser's sums are in h_tot
   // timers
   std::vector<hipEvent_t> evpool;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-  std::vector<int> pending_wide;   // the pass ran 9..16 columns (16x16x4 MFMA)
+  PassLedger ledger;
   // cross-rank exchange counters (sgv_exchange_stats): all-gathers issued, the
   // bytes each rank contributed, and their time -- HIP events around every
   // ncclAllGather on the ctx stream (the wait for the slowest peer included),
@@ -403,12 +440,6 @@ struct sgv_ctx {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> gpending;   // exact-CG read gaps
   std::vector<std::pair<hipEvent_t, hipEvent_t>> empending;  // EM loops
   double xchg_n = 0.0, xchg_ms = 0.0, xchg_bytes = 0.0;
-  double ld_ms = 0.0, ld_launches = 0.0, rhs_bytes = 0.0, ld_bytes = 0.0, dense_bytes = 0.0,
-         aux_bytes = 0.0;
-  // algorithmic flops of the passes (2 per multiply-add: row part of every stored
-  // element, column part of the packed off-diagonal-block ones), and the 9..16-
-  // column passes' share (their bound is the f64 matrix core, not HBM)
-  double ld_flops = 0.0, ld_flops_wide = 0.0, ld_ms_wide = 0.0, ld_launches_wide = 0.0;
   std::string err;
 };
 
@@ -488,6 +519,74 @@ int grow(sgv_ctx* c, double** buf, size_t* cap, size_t need);
 int ensure_plan(sgv_ctx* c, int ld);
 const int* ld_parts(sgv_ctx* c, int ld);
 int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in);
+
+// The columns of one LD pass: of columns 0 .. ncol - 1 those that take(j)
+// accepts, in column order; fill(pa, n, j) fills slot n of the PassArgs from
+// column j, and map sends slot n's partial dot to column j (reduce_dev).
+struct PassCols {
+  PassArgs pa{};
+  Map16 map = identity_map();
+  int nc = 0;
+};
+template <class Take, class Fill>
+static inline PassCols gather_cols(int ncol, Take take, Fill fill) {
+  PassCols pc;
+  for (int j = 0; j < ncol; ++j) {
+    if (!take(j)) continue;
+    fill(pc.pa, pc.nc, j);
+    pc.map.d[pc.nc] = j;
+    ++pc.nc;
+  }
+  return pc;
+}
+
+// The cohorts in groups of MAXK (one kernel launch takes at most MAXK):
+// f(g, k0, Kg) for group g, the cohorts k0 .. k0 + Kg - 1, in order
+static inline int cohort_groups(int K) { return (K + MAXK - 1) / MAXK; }
+template <class F>
+static inline int for_cohort_groups(int K, F f) {
+  for (int g = 0, k0 = 0; k0 < K; ++g, k0 += MAXK) CHK(f(g, k0, std::min(MAXK, K - k0)));
+  return SGV_OK;
+}
+
+// cg.hip
+// the columns of a batched CG: column c uses LD matrix col_ld[c], A = c1[c] R + c2[c] I
+struct CgCols {
+  int ncol = 0;
+  int col_ld[MAXC];
+  double c1[MAXC], c2[MAXC];
+  double* X[MAXC];
+  double* Rr[MAXC];
+  double* P[MAXC];
+  double* Q[MAXC];
+  double* RX[MAXC] = {};   // non-null: carry R_s x (RX += alpha R_s p), Y = R_s p scratch
+  double* Y[MAXC] = {};
+  double s = 0.0;          // ridge of R_s
+};
+// the CG prologue's sums riding in iteration 0's exchange (cg_loop_dev)
+struct CgMerge0 {
+  const double* part = nullptr;   // [chunk][2 MAXC] (k_lmmse_init)
+  double rtol = 0.0;
+  double* const* X = nullptr;     // k_cg_init zeroes X, R_s X of |b| == 0 columns
+  double* const* RX = nullptr;
+};
+// the CG prologue's scalars on the host (iterative.py:376-392) from bb[j] = |b|^2
+// and rr[j] = |r0|^2: atol, rho, and active[j] = 0 where |b| == 0 (the caller sets
+// that column's x = b)
+void cg_prologue(int ncol, const double* bb, const double* rr, double rtol, double* atol,
+                 double* rho, int* active);
+int cg_loop_dev(sgv_ctx* c, const CgCols& cc, const double* rho0, const double* atol, int maxiter,
+                const int* active_in, int* iters, int* info, int* passes,
+                const CgMerge0* m0 = nullptr);
+int cg_run(sgv_ctx* c, const CgCols& cc, double* rho, const double* atol, int maxiter,
+           const int* active, int* iters, int* info, int* passes);
+int event_spin(sgv_ctx* c, hipEvent_t ev);   // spin on an event already recorded on the ctx stream
+// prior.hip
+int denoise_enqueue(sgv_ctx* c, const double* gam1s, const double* a, double lam, int nslab,
+                    const double* omegas, const double* sigmas, double rho, int damp,
+                    bool metrics = false, bool* fused = nullptr);
+int posterior_enqueue(sgv_ctx* c, const double* gam1s, const double* a, double lam, int nslab,
+                      const double* omegas, const double* sigmas, double thr, bool resp);
 
 // a host table -> a new device array (*d; nothing for an empty table)
 template <typename T>

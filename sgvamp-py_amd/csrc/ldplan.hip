@@ -812,7 +812,7 @@ static int coupling_pass(sgv_ctx* c, const LdPlan& pl, int nc, const PassArgs& p
   if (pl.nctasks)
     HIPCHK(launch_coupling(nc, pl.d_ctasks, pl.nctasks, pa, recv, pl.hmax, c->d_cpbuf, pl.ncp,
                            c->st));
-  c->aux_bytes += pl.cpl_bytes + 2.0 * 8.0 * nc * 256.0 * pl.ncp;
+  c->ledger.n.aux_bytes += pl.cpl_bytes + 2.0 * 8.0 * nc * 256.0 * pl.ncp;
   return SGV_OK;
 }
 
@@ -855,23 +855,15 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
   const PassForm f = plan_form(pl, nc, c->mfma_min);
   PassArgs pa = pa_in;
   pa.cpbuf = c->d_cpbuf;
-  hipEvent_t e0, e1;
-  if (c->evpool.size() < 2) {
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-  } else {
-    e0 = c->evpool.back();
-    c->evpool.pop_back();
-    e1 = c->evpool.back();
-    c->evpool.pop_back();
-  }
+  hipEvent_t e0, e1;   // the pass's pair in the ledger
+  CHK(event_pair(c, &e0, &e1));
   HIPCHK(hipEventRecord(e0, c->st));
   if (f.kind == PK_FACTOR) {   // before the stored forms: the plan holds nothing of theirs
     for (const LdPlan::FacLaunch& fl : pl.fac_launch)   // stream order: the scratch is reused
       HIPCHK(launch_geno_factor(nc, pl.d_fac + fl.b0, fl.nb, fl.gx_t, fl.gy_t, fl.gx_q, pa, c->d_pk,
                                 c->d_ft, c->d_ftp, c->d_part, c->st));
     // t, the slab partials and the interleaved right-hand sides, written and read
-    c->aux_bytes += 2.0 * 8.0 * nc * (pl.fac_scratch + (double)c->Mloc);
+    c->ledger.n.aux_bytes += 2.0 * 8.0 * nc * (pl.fac_scratch + (double)c->Mloc);
   }
   if (pl.halo || pl.nctasks) CHK(coupling_pass(c, pl, nc, pa));
   if (f.dense) HIPCHK(launch_ld_pass(nc, c->d_blks[ld], pl.d_rg, pl.nrg, pa, c->d_part, c->st));
@@ -882,7 +874,7 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
     HIPCHK(launch_sym_finalize(nc, cls, pl.d_panels[cls], pl.npanels, pa, c->d_rowpart,
                                c->d_colpart, c->d_part, c->st));
     const double cw = (double)(1024 >> cls);
-    c->aux_bytes += 2.0 * 8.0 * nc * (double)pl.nitems[cls] * (SYM_H + cw);
+    c->ledger.n.aux_bytes += 2.0 * 8.0 * nc * (double)pl.nitems[cls] * (SYM_H + cw);
   } else if (f.kind != PK_NONE && f.kind != PK_FACTOR) {
     HIPCHK(launch_pk(pa, nc, c->Mpad, c->d_pk, f.pk_width, f.pk_paired, c->st));
     if (f.kind == PK_WALK) {   // band plan: the walks, then the head panels
@@ -890,7 +882,7 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
                               f.pk_width, c->Mpad, pa, c->d_whead, c->d_wcarry, pl.d_wfins,
                               pl.nwfins, c->d_part, pl.bits, f.load_form, c->st));
       // head partials and carries, written and read
-      c->aux_bytes += 2.0 * 8.0 * nc * SYM_H * (double)(pl.nhslots + pl.ncslots);
+      c->ledger.n.aux_bytes += 2.0 * 8.0 * nc * SYM_H * (double)(pl.nhslots + pl.ncslots);
     } else {
       // One strip set: group g's strips on the ctx stream, its finalize on the
       // side stream behind them, so the finalize (and the launch tail) of g
@@ -930,13 +922,13 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
           CHK(run_set(pl.rest, f.rest_kind, f.rest_side,
                       c->d_rowpart + (size_t)pl.wide.nslots_items * SYM_H * nc,
                       c->d_colpart + (size_t)pl.wide.nstrips * MFW_CW * nc));
-        c->aux_bytes += 2.0 * 8.0 * nc * ((double)pl.wide.nsitems * SYM_H +
+        c->ledger.n.aux_bytes += 2.0 * 8.0 * nc * ((double)pl.wide.nsitems * SYM_H +
                                           (double)pl.wide.nstrips * MFW_CW +
                                           (double)pl.rest.nsitems * SYM_H +
                                           (double)pl.rest.nstrips * 512);
       } else {
         CHK(run_set(pl.s512, f.kind, f.side, c->d_rowpart, c->d_colpart));
-        c->aux_bytes += 2.0 * 8.0 * nc * ((double)pl.s512.nsitems * SYM_H +
+        c->ledger.n.aux_bytes += 2.0 * 8.0 * nc * ((double)pl.s512.nsitems * SYM_H +
                                           (double)pl.s512.nstrips * 512);
       }
       if (f.side || f.rest_side) {
@@ -944,20 +936,21 @@ int ld_pass(sgv_ctx* c, int ld, int nc, const PassArgs& pa_in){
         HIPCHK(hipStreamWaitEvent(c->st, c->ev_fin, 0));
       }
     }
-    c->aux_bytes += 8.0 * (double)c->Mpad * (f.pk_width + nc);   // Pk pack
+    c->ledger.n.aux_bytes += 8.0 * (double)c->Mpad * (f.pk_width + nc);   // Pk pack
   }
   HIPCHK(hipEventRecord(e1, c->st));
-  c->pending.emplace_back(e0, e1);
-  c->pending_wide.push_back(f.mfma16 ? 1 : 0);
-  c->ld_flops += 2.0 * nc * pl.mac_elems;
+  PassLedger& led = c->ledger;
+  led.pending.emplace_back(e0, e1);
+  led.pending_wide.push_back(f.mfma16 ? 1 : 0);
+  led.n.flops += 2.0 * nc * pl.mac_elems;
   if (f.mfma16) {
-    c->ld_flops_wide += 2.0 * nc * pl.mac_elems;
-    c->ld_launches_wide += 1.0;
+    led.n.flops_wide += 2.0 * nc * pl.mac_elems;
+    led.n.launches_wide += 1.0;
   }
-  c->ld_launches += 1.0;
-  c->ld_bytes += pl.stored_bytes;
-  c->dense_bytes += pl.dense_bytes;
-  c->rhs_bytes += 2.0 * nc * (double)c->Mloc * 8.0;
+  led.n.launches += 1.0;
+  led.n.bytes += pl.stored_bytes;
+  led.n.dense_bytes += pl.dense_bytes;
+  led.n.rhs_bytes += 2.0 * nc * (double)c->Mloc * 8.0;
   return SGV_OK;
 }
 

@@ -165,7 +165,7 @@ def t1_case(shape, cfg, s):
 
 def host_scalars(sums, gamw, gam2, a2prev, N, Mtot, damp, learn, rho=RHO1):
     """The output row of one cohort from its four sums: the library's f64
-    expressions in its order (solver.hip, lmmse_group)."""
+    expressions in its order (solver.hip: lmmse_group, gamw_outputs)."""
     TrS = np.float64(sums["TrS"])
     with np.errstate(divide="ignore", invalid="ignore"):
         a2 = gam2 * TrS / float(Mtot)

@@ -425,3 +425,27 @@ def test_cg_scaled_columns_stop_together(part):
         h = _solve(eng, False, exact, c1, c2, B, X0, 500)
         assert p[1].tolist() == [it_r] * 6 and p[2].tolist() == [info_r] * 6, (exact, p[1], p[2])
         _same_cg(p, h, "scaled columns, exact=%d" % exact)
+
+
+@pytest.mark.parametrize("part", ["mixed8", "mixed9"])
+def test_pass_ledger_is_the_same_in_every_loop(part):
+    """The pass counters of timers() over one six-column solve, in the four
+    (pipelined, exact) arms, on the fused (mixed8) and the two-launch (mixed9)
+    control path: ld_launches is the warm-start pass of the last column plus one
+    pass per CG iteration of the slowest column -- the pipelined loop's no-op
+    look-ahead iteration is rolled back, not counted; ld_bytes is the same in
+    every arm, rhs_bytes in the two exact arms (the same column sets)."""
+    eng, _, bounds = _cg_system(part)
+    c1, c2, B, X0 = _columns(int(bounds[-1]), 6)
+    led = {}
+    for pipe in (True, False):
+        for exact in (0, 1):
+            eng.timers(reset=True)
+            _, it, _ = _solve(eng, pipe, exact, c1, c2, B, X0, 500)
+            t = eng.timers()
+            print(part, pipe, exact, "iters", it.tolist(), "launches", t["ld_launches"],
+                  "ld_bytes", t["ld_bytes"], "rhs_bytes", t["rhs_bytes"])
+            assert t["ld_launches"] == 1 + int(it.max()), (pipe, exact, t["ld_launches"], it)
+            led[(pipe, exact)] = t
+    assert len({t["ld_bytes"] for t in led.values()}) == 1, led
+    assert led[(True, 1)]["rhs_bytes"] == led[(False, 1)]["rhs_bytes"], led

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Bitwise A/B of two builds: run fixed LD passes (packed VALU/MFMA, dense, the
 wide-item block sizes, band; the last two also f32-stored), full VAMP runs of
-golden cases and every LD form built from .bed genotypes through the library at
---lib, print one SHA-256 per result.  Two builds whose lines are equal produce the
+golden cases, every LD form built from .bed genotypes and the solver's host
+paths (LMMSE steps in every mode, the CG loops, the EM loops, the pass ledger)
+through the library at --lib, print one SHA-256 per result.  Two builds whose lines are equal produce the
 same bits (under the same SGV_AB switches: run it once per arm).
 
   python tools/ab_bitwise.py --lib sgvamp-py_amd/libsgvamp_hip.so > a.txt
@@ -84,6 +85,127 @@ def geno(Engine):
                                     np.clip(W - nr + np.arange(nr) + 1, 0, nc))
             ck = corner(eng)
             print("geno %s corner W=%d window %s keep %s" % (tag, W, cw, ck))
+        eng.close()
+
+
+def hh(*parts):
+    """One hash over several results (arrays, scalars, lists), in order."""
+    return h(np.concatenate([np.asarray(p, dtype=np.float64).ravel() for p in parts]))
+
+
+def ledger(eng):
+    """The pass ledger's counts and bytes (timers() without its millisecond
+    slots), read and cleared."""
+    t = eng.timers(reset=True)
+    return [t[k] for k in ("ld_launches", "ld_bytes", "rhs_bytes", "dense_bytes", "aux_bytes",
+                           "ld_flops", "wide_flops", "wide_launches")]
+
+
+def solver(Engine, VAMP, BlockLD, Case):
+    """The host code that drives the CG, the LMMSE step and the EM loop (cg.hip,
+    solver.hip, prior.hip): every line hashes the outputs with cg_out, the pass
+    count and the ledger."""
+    import hip_backend as hb
+    from tests import lmmse_ref as lr
+    from tests import marker_ref as mr
+    from tests import test_gpu_marker_kernels as tm
+
+    def lmmse_calls(eng, shape, K, rs, pipe, damp, learn):
+        """Three consecutive calls: cold; warm (and damped); new gamw / gam2."""
+        d = lr.t2_inputs(shape)
+        eng.reset_solver()
+        eng.set_rs_recurrence(rs)
+        eng.set_cg_pipeline(pipe)
+        eng.timers(reset=True)
+        parts = []
+        for n in range(3):
+            gamw = [g * (1.7 if n == 2 else 1.0) for g in d["gamw"][:K]]
+            gam2 = [g * (0.6 if n == 2 else 1.0) for g in d["gam2"][:K]]
+            eng.set_vector(hb.VEC_XHAT1, 0, d["xhat1"])
+            for k in range(K):
+                eng.set_cohort_n(k, d["N"][k])
+                eng.set_vector(hb.VEC_R, k, d["r"][k])
+                eng.set_vector(hb.VEC_R1, k, d["r1"][n][k])
+            out, cg, passes = eng.lmmse(n, gamw, gam2, d["alpha1"][n][:K], d["a2prev"][:K],
+                                        d["u"][n][:K], lr.T2_MAXIT, damp and n > 0, lr.T2_RHO,
+                                        learn, rtol=lr.T2_RTOL)
+            parts += [out, cg, [passes], ledger(eng)]
+            for which in (hb.VEC_XHAT2, hb.VEC_SIG2U, hb.VEC_R1):
+                parts += [eng.get_vector(which, k) for k in range(K)]
+        return hh(*parts)
+
+    def lmmse_engine(shape, ld_of, exchange=None):
+        S = lr.system(shape)
+        eng = Engine(S.sizes, K=len(ld_of), ld_of=ld_of, exchange=exchange)
+        S.upload(eng, sorted(set(ld_of)))
+        eng.set_ridge(S.s)
+        return eng
+
+    modes = [(rs, pipe, damp, learn) for rs in (1, 0) for pipe in (1, 0) for damp in (0, 1)
+             for learn in (0, 1)]
+    for shape in lr.T2_SHAPES:        # cohorts 0 and 2 share an LD matrix, cohort 1 has its own
+        eng = lmmse_engine(shape, lr.T2_LD_OF)
+        for m in modes:
+            print("solver lmmse %s K3 distinct rs=%d pipe=%d damp=%d learn=%d %s"
+                  % ((shape,) + m + (lmmse_calls(eng, shape, 3, *m),)))
+        eng.close()
+    eng = lmmse_engine("mixed9", [0, 0, 0])      # one pass of 6 columns: the exact column sets
+    for exact in (0, 1):
+        eng.ctx.sgv_set_cg_exact(exact)
+        for m in ((1, 1, 1, 1), (1, 0, 1, 1), (0, 1, 0, 1)):
+            print("solver lmmse mixed9 K3 shared exact=%d rs=%d pipe=%d damp=%d learn=%d %s"
+                  % ((exact,) + m + (lmmse_calls(eng, "mixed9", 3, *m),)))
+    eng.close()
+    for K in (1, 2):                  # the one-rank host exchange: CgMerge0 at one LD matrix
+        eng = lmmse_engine(lr.T3_SHAPE, lr.T2_LD_OF[:K], exchange="host")
+        for m in ((1, 1, 1, 1), (0, 1, 0, 1), (1, 0, 1, 0)):
+            print("solver lmmse %s K%d rehearsal rs=%d pipe=%d damp=%d learn=%d %s"
+                  % ((lr.T3_SHAPE, K) + m + (lmmse_calls(eng, lr.T3_SHAPE, K, *m),)))
+        eng.close()
+    for name in ("k10_shared", "k11_distinct"):   # more than MAXKG cohorts: two LMMSE groups
+        c = Case(name)
+        f = c.flags
+        lds = [BlockLD(bl, s=f["s"]) for bl in c.ld_blocks]
+        R = lds[0] if len(lds) == 1 else [lds[c.ld_of[k]] for k in range(c.K)]
+        Nt = sum(c.N)
+        with tempfile.TemporaryDirectory() as d:
+            v = VAMP(N=c.N, Nt=Nt, M=c.M, K=c.K, rho=f["rho"], gamw=f["gamw"], gam1=f["gam1"],
+                     a=np.array(c.N) / Nt, prior_vars=f["prior_vars"],
+                     prior_probs=f["prior_probs"], out_dir=d, out_name=name, seed=f["seed"])
+            xh = v.infer(R, c.r, f["iterations"], x0=c.x0, cg_maxit=f["cg_maxit"],
+                         em_prior_maxit=f["em_prior_maxit"], learn_gamw=f["learn_gamw"],
+                         lmmse_damp=f["lmmse_damp"], prior_update=f["prior_update"],
+                         update_prior_from=f["update_prior_from"])
+            print("solver vamp %s %s" % (name, hh(np.array(xh), [r["cg_iters"] for r in v.history],
+                                                  ledger(v.engine))))
+            v.engine.close()
+    for part in ("edges", "mixed13"):            # the fused and the two-launch EM control
+        for K, nslab in ((3, 3), (33, 2)):       # one and two cohort groups
+            c = mr.case(("benign", 0, K, nslab), sum(mr.PARTS[part]))
+            eng = Engine(mr.PARTS[part], K=K)
+            for k, r in enumerate(c["r1s"]):
+                eng.set_vector(hb.VEC_R1, k, r)
+            for pipe in (1, 0):
+                eng.set_cg_pipeline(pipe)
+                got = [eng.em(c["gam1s"], c["a"], c["sigmas"], maxit, c["lam"], c["omegas"])
+                       for maxit in (25, 1, 3)]
+                print("solver em %s K=%d pipe=%d %s" % (part, K, pipe,
+                                                      hh(*[x for g in got for x in g])))
+            eng.close()
+    for part in ("mixed8", "mixed9"):            # the fused and the two-launch CG control
+        eng, _, bounds = tm._cg_system(part)
+        M = int(bounds[-1])
+        for pipe in (1, 0):
+            for maxiter in (3, 4, 5):            # the mirror ring's boundary
+                eng.timers(reset=True)
+                X, it, info = tm._solve(eng, pipe, 0, *tm._columns(M, 2), maxiter)
+                print("solver cg %s pipe=%d maxiter=%d %s" % (part, pipe, maxiter,
+                                                             hh(X, it, info, ledger(eng))))
+            for exact in (0, 1):
+                eng.timers(reset=True)
+                X, it, info = tm._solve(eng, pipe, exact, *tm._columns(M, 6), 500)
+                print("solver cg %s pipe=%d exact=%d 6 columns %s" % (part, pipe, exact,
+                                                                     hh(X, it, info, ledger(eng))))
         eng.close()
 
 
@@ -185,6 +307,7 @@ def main():
             print("vamp %s %s" % (name, h(np.array(xh))))
             v.engine.close()
     geno(Engine)
+    solver(Engine, VAMP, BlockLD, Case)
 
 
 if __name__ == "__main__":
