@@ -409,6 +409,51 @@ int sgv_geno_coupling_reach(sgv_ctx* ctx, int ld, int gb, int nr, int nc, const 
                             int64_t row_bytes, int nsamp, const int32_t* keep, const double* pos,
                             double span, int64_t* counts_out);
 
+/* ---- scoring: a target .bed panel against saved effects ---------------------
+ * gVAMP's `test` run mode: S[n][c] = sum_i X[i][n] B[i][c] over a stream of marker
+ * chunks of a TARGET panel of nsamp samples (any panel: no LD needs to be set, and
+ * the LD, the staged genotype blocks, the vectors and the timers of a context that
+ * has them are not touched), for ncol = 1..SGV_SCORE_MAXCOL effect columns, on the
+ * f64 matrix cores from the 2-bit rows (csrc/score.hip).  X[i][n] = tab_i[code_in],
+ * rows and codes as in "genotype LD source" above.
+ * sgv_score_begin starts a stream (a stream in progress is dropped) with S = +0.
+ * sgv_score_chunk adds the next n markers: rows (n rows, row_bytes apart, >=
+ * ceil(nsamp / 4)), column c's n effects at beta + c ldb (ldb >= n when ncol > 1),
+ * counts_out[i * 4 + code] as sgv_geno_set_block fills it (n x 4), and tab_i by mode:
+ *   SGV_SCORE_TARGET  from the chunk's own exact counts: (x - mean) / sd with the
+ *                     mean and sd defined above, missing -> 0, no 1 / sqrt(nsamp); a
+ *                     marker that is monomorphic or unobserved in the target gets a
+ *                     zero table (it scores 0; the caller finds it in the counts);
+ *   SGV_SCORE_RAW     the A1 dosage 2 / 1 / 0, missing -> S1 / n_obs (0 if unobserved);
+ *   SGV_SCORE_TABLE   the caller's tab[n][4] (by code 0..3), every entry finite.
+ * tab is read in SGV_SCORE_TABLE mode only.  Every chunk but the stream's last
+ * holds a multiple of 1,024 markers.
+ * sgv_score_end writes scores_out[c * nsamp + n] = S[n][c] and ends the stream.
+ * Order of every sum: markers are cut into slabs of 1,024 by their index in the
+ * stream; a slab's partial starts from +0 and takes its markers four at a time in
+ * ascending order; S is the slab partials added left to right in ascending slab
+ * order across chunk boundaries.  So a result is bitwise independent of the chunk
+ * lengths, of the device and of which columns share a call, and the bits past
+ * sample nsamp of a row never reach it.
+ * SGV_ERR_ARG: nsamp < 1, ncol outside 1..SGV_SCORE_MAXCOL, a null or short array,
+ * an unknown mode, a non-finite tab entry, or a chunk after one that was not a
+ * multiple of 1,024 markers; SGV_ERR_STATE: sgv_score_chunk or sgv_score_end without
+ * sgv_score_begin.  A refusal leaves the stream and the context as they were.
+ * sgv_score_timers, since the last reset: t[0] = ms of the stream's kernels (HIP
+ * events), t[1] = chunks, t[2] = 2 nsamp n ncol flops summed over chunks, t[3] = host
+ * ms spent staging (repacking rows, uploads, counts); writes min(cap,
+ * SGV_SCORE_TIMERS_N) values. */
+#define SGV_SCORE_MAXCOL 64
+#define SGV_SCORE_TARGET 0
+#define SGV_SCORE_RAW 1
+#define SGV_SCORE_TABLE 2
+#define SGV_SCORE_TIMERS_N 4
+int sgv_score_begin(sgv_ctx* ctx, int nsamp, int ncol);
+int sgv_score_chunk(sgv_ctx* ctx, const uint8_t* rows, int64_t row_bytes, int n, int mode,
+                    const double* tab, const double* beta, int64_t ldb, int64_t* counts_out);
+int sgv_score_end(sgv_ctx* ctx, double* scores_out /* ncol x nsamp */);
+int sgv_score_timers(sgv_ctx* ctx, double* t, int cap, int reset);
+
 /* ---- Hutchinson probes (host only, no device) ----------------------------
  * src/sgvamp.py:326 u = np.random.binomial(p=1/2, n=1, size=n)*2-1 from a legacy
  * numpy RandomState (MT19937) whose state is key[624], *pos (as

@@ -5,6 +5,7 @@
 // parts: exchange.hip, ldplan.hip, cg.hip, prior.hip, solver.hip (ctx.h lists
 // them).
 #include "ctx.h"
+#include "score.h"
 
 static thread_local std::string g_last_err;
 
@@ -418,6 +419,13 @@ extern "C" void sgv_destroy(sgv_ctx* c) {
   if (c->d_rowpart) (void)hipFree(c->d_rowpart);
   if (c->d_ft) (void)hipFree(c->d_ft);
   if (c->d_ftp) (void)hipFree(c->d_ftp);
+  for (double* p : {c->score.d_S, c->score.d_part, c->score.d_rows, c->score.d_tab,
+                    c->score.d_beta})
+    if (p) (void)hipFree(p);
+  for (auto& pr : c->score.pending) {
+    (void)hipEventDestroy(pr.first);
+    (void)hipEventDestroy(pr.second);
+  }
   if (c->d_whead) (void)hipFree(c->d_whead);
   if (c->d_wcarry) (void)hipFree(c->d_wcarry);
   if (c->d_colpart) (void)hipFree(c->d_colpart);
@@ -1107,6 +1115,168 @@ extern "C" int sgv_geno_g(sgv_ctx* c, const double* beta, double* g_out) {
     CHK(stream_wait(c));
     std::memcpy(g_out + (size_t)b * nsamp, c->h_stage, sizeof(double) * nsamp);
   }
+  return SGV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// scoring a target panel with saved effects (score.hip)
+// ---------------------------------------------------------------------------
+static void score_resolve(sgv_ctx* c) {
+  resolve_pairs(c, c->score.pending, [&](float ms, size_t) { c->score.ms += ms; });
+}
+
+extern "C" int sgv_score_begin(sgv_ctx* c, int nsamp, int ncol) {
+  ENTER(c);
+  if (nsamp < 1 || ncol < 1 || ncol > SGV_SCORE_MAXCOL)
+    return fail(c, SGV_ERR_ARG, "sgv_score_begin: bad arguments (%d samples, %d columns; 1..%d "
+                "columns)", nsamp, ncol, SGV_SCORE_MAXCOL);
+  ScoreState& s = c->score;
+  const size_t need = (size_t)((ncol + SC_COLS - 1) / SC_COLS) * nsamp * SC_COLS;
+  CHK(stream_wait(c));
+  s.active = false;   // a stream in progress is dropped: its S may be released by grow
+  CHK(grow(c, &s.d_S, &s.S_cap, need));
+  HIPCHK(hipMemsetAsync(s.d_S, 0, sizeof(double) * need, c->st));
+  CHK(stream_wait(c));
+  s.active = true;
+  s.nsamp = nsamp;
+  s.ncol = ncol;
+  s.seen = 0;
+  return SGV_OK;
+}
+
+extern "C" int sgv_score_chunk(sgv_ctx* c, const uint8_t* rows, int64_t row_bytes, int n, int mode,
+                               const double* tab, const double* beta, int64_t ldb,
+                               int64_t* counts_out) {
+  ENTER(c);
+  ScoreState& s = c->score;
+  if (!s.active)
+    return fail(c, SGV_ERR_STATE, "sgv_score_chunk: no scoring stream (sgv_score_begin)");
+  const int nsamp = s.nsamp, ncol = s.ncol;
+  if (!rows || !beta || !counts_out || n < 1 || row_bytes < ((int64_t)nsamp + 3) / 4 ||
+      (ncol > 1 && ldb < n) || mode < SGV_SCORE_TARGET || mode > SGV_SCORE_TABLE ||
+      (mode == SGV_SCORE_TABLE && !tab))
+    return fail(c, SGV_ERR_ARG, "sgv_score_chunk: bad arguments (%d markers, rows of %lld bytes "
+                "for %d samples, mode %d, ldb %lld)", n, (long long)row_bytes, nsamp, mode,
+                (long long)ldb);
+  if (s.seen % SC_SLAB != 0)
+    return fail(c, SGV_ERR_ARG, "sgv_score_chunk: the stream holds %lld markers, not a multiple of "
+                "%d: only its last chunk may be ragged", (long long)s.seen, SC_SLAB);
+  if (mode == SGV_SCORE_TABLE)
+    for (int64_t k = 0; k < 4 * (int64_t)n; ++k)
+      if (!std::isfinite(tab[k]))
+        return fail(c, SGV_ERR_ARG, "sgv_score_chunk: tab[%lld][%d] is not finite",
+                    (long long)(k / 4), (int)(k % 4));
+  // everything below can fail only in the runtime
+  const auto h0 = std::chrono::steady_clock::now();
+  const int64_t used = ((int64_t)nsamp + 3) / 4;
+  const int64_t stride_w = ((int64_t)nsamp + 15) / 16;
+  const size_t bits_bytes = (size_t)n * stride_w * 4;
+  const size_t cnt_bytes = sizeof(long long) * 4 * (size_t)n;
+  const size_t tab_bytes = sizeof(double) * 4 * (size_t)n;
+  const size_t beta_bytes = sizeof(double) * (size_t)ncol * n;
+  CHK(grow(c, &s.d_rows, &s.rows_cap, (bits_bytes + 7) / 8));
+  CHK(grow(c, &s.d_tab, &s.tab_cap, (size_t)14 * n));
+  CHK(grow(c, &s.d_beta, &s.beta_cap, (size_t)(ncol + SC_COLS) * n));
+  uint32_t* d_bits = reinterpret_cast<uint32_t*>(s.d_rows);
+  double* d_tab = s.d_tab;
+  double* d_lut = s.d_tab + 4 * (size_t)n;
+  double* d_msd = s.d_tab + 8 * (size_t)n;
+  long long* d_cnt = reinterpret_cast<long long*>(s.d_tab + 10 * (size_t)n);
+  double* d_beta = s.d_beta;
+  double* d_pk = s.d_beta + (size_t)ncol * n;
+  CHK(ensure_hstage(c, std::max(std::max(bits_bytes, cnt_bytes), std::max(tab_bytes, beta_bytes))));
+  // rows need not be word aligned at the caller: repacked to whole words
+  uint8_t* hs = static_cast<uint8_t*>(c->h_stage);
+  std::memset(hs, 0, bits_bytes);
+  for (int64_t i = 0; i < n; ++i)
+    std::memcpy(hs + (size_t)i * stride_w * 4, rows + (size_t)i * row_bytes, (size_t)used);
+  HIPCHK(hipMemcpyAsync(d_bits, hs, bits_bytes, hipMemcpyHostToDevice, c->st));
+  HIPCHK(launch_bed_stats(d_bits, stride_w, n, nsamp, d_cnt, d_lut, d_msd, c->st));
+  CHK(stream_wait(c));   // the bits have left the staging buffer
+  HIPCHK(hipMemcpyAsync(c->h_stage, d_cnt, cnt_bytes, hipMemcpyDeviceToHost, c->st));
+  CHK(stream_wait(c));
+  {
+    const long long* hc = static_cast<const long long*>(c->h_stage);
+    for (int64_t k = 0; k < 4 * (int64_t)n; ++k) counts_out[k] = (int64_t)hc[k];
+  }
+  if (mode == SGV_SCORE_TABLE) {
+    std::memcpy(c->h_stage, tab, tab_bytes);
+    HIPCHK(hipMemcpyAsync(d_tab, c->h_stage, tab_bytes, hipMemcpyHostToDevice, c->st));
+    CHK(stream_wait(c));
+  } else {
+    HIPCHK(launch_score_tab(mode, d_cnt, d_msd, n, d_tab, c->st));
+  }
+  {
+    double* hb = static_cast<double*>(c->h_stage);
+    for (int j = 0; j < ncol; ++j)
+      std::memcpy(hb + (size_t)j * n, beta + (size_t)j * ldb, sizeof(double) * n);
+    HIPCHK(hipMemcpyAsync(d_beta, hb, beta_bytes, hipMemcpyHostToDevice, c->st));
+    CHK(stream_wait(c));
+  }
+  // slabs of one launch: the partials stay under SC_PART_MAX doubles
+  const int64_t nslab = ((int64_t)n + SC_SLAB - 1) / SC_SLAB;
+  const int64_t per = std::max<int64_t>(
+      1, std::min<int64_t>(std::min<int64_t>(nslab, 65535), SC_PART_MAX / ((int64_t)nsamp * SC_COLS)));
+  CHK(grow(c, &s.d_part, &s.part_cap, (size_t)per * nsamp * SC_COLS));
+  s.stage_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0)
+                    .count();
+  hipEvent_t e0, e1;
+  CHK(event_pair(c, &e0, &e1));
+  HIPCHK(hipEventRecord(e0, c->st));
+  for (int g = 0; g * SC_COLS < ncol; ++g) {
+    HIPCHK(launch_score_pack(d_beta, n, ncol, g * SC_COLS, d_pk, c->st));
+    double* d_Sg = s.d_S + (size_t)g * nsamp * SC_COLS;
+    for (int64_t s0 = 0; s0 < nslab; s0 += per) {
+      const int ns = (int)std::min<int64_t>(per, nslab - s0);
+      const int64_t m0 = s0 * SC_SLAB;
+      const int nm = (int)std::min<int64_t>((int64_t)n - m0, (int64_t)ns * SC_SLAB);
+      HIPCHK(launch_score_mfma(d_bits + m0 * stride_w, stride_w, d_tab + 4 * m0,
+                               d_pk + SC_COLS * m0, nm, ns, nsamp, s.d_part, c->st));
+      HIPCHK(launch_score_sum(s.d_part, ns, nsamp, d_Sg, c->st));
+    }
+  }
+  HIPCHK(hipEventRecord(e1, c->st));
+  s.pending.emplace_back(e0, e1);
+  CHK(stream_wait(c));
+  score_resolve(c);
+  s.seen += n;
+  s.chunks += 1.0;
+  s.flops += 2.0 * (double)nsamp * (double)n * (double)ncol;
+  return SGV_OK;
+}
+
+extern "C" int sgv_score_end(sgv_ctx* c, double* scores_out) {
+  ENTER(c);
+  ScoreState& s = c->score;
+  if (!s.active)
+    return fail(c, SGV_ERR_STATE, "sgv_score_end: no scoring stream (sgv_score_begin)");
+  if (!scores_out) return fail(c, SGV_ERR_ARG, "sgv_score_end: null output");
+  const size_t per = (size_t)s.nsamp * SC_COLS;
+  CHK(ensure_hstage(c, sizeof(double) * per));
+  for (int g = 0; g * SC_COLS < s.ncol; ++g) {
+    HIPCHK(hipMemcpyAsync(c->h_stage, s.d_S + g * per, sizeof(double) * per, hipMemcpyDeviceToHost,
+                          c->st));
+    CHK(stream_wait(c));
+    const double* h = static_cast<const double*>(c->h_stage);
+    const int nc = std::min(SC_COLS, s.ncol - g * SC_COLS);
+    for (int j = 0; j < nc; ++j) {
+      double* o = scores_out + (size_t)(g * SC_COLS + j) * s.nsamp;
+      for (int64_t k = 0; k < s.nsamp; ++k) o[k] = h[k * SC_COLS + j];
+    }
+  }
+  s.active = false;
+  return SGV_OK;
+}
+
+extern "C" int sgv_score_timers(sgv_ctx* c, double* t, int cap, int reset) {
+  ENTER(c);
+  if (!t || cap < 0) return fail(c, SGV_ERR_ARG, "sgv_score_timers: bad arguments");
+  ScoreState& s = c->score;
+  CHK(stream_wait(c));
+  score_resolve(c);
+  const double v[SGV_SCORE_TIMERS_N] = {s.ms, s.chunks, s.flops, s.stage_ms};
+  for (int i = 0; i < std::min(cap, SGV_SCORE_TIMERS_N); ++i) t[i] = v[i];
+  if (reset) s.ms = s.chunks = s.flops = s.stage_ms = 0.0;
   return SGV_OK;
 }
 

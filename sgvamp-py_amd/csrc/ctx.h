@@ -82,6 +82,24 @@ struct GenoBlock {
   int64_t nbad = 0;              // markers without LD (monomorphic or unobserved)
 };
 
+// one scoring stream (sgv_score_begin / _chunk / _end: capi.hip, score.hip).  Its
+// buffers are its own (grow()): nothing of the LD, the staged genotypes or the
+// solver is touched.
+struct ScoreState {
+  bool active = false;
+  int nsamp = 0, ncol = 0;
+  int64_t seen = 0;              // markers streamed so far (the next chunk's global index)
+  double* d_S = nullptr;         // the running S [column group][nsamp][16]
+  double* d_part = nullptr;      // one launch's slab partials [slab][nsamp][16]
+  double* d_rows = nullptr;      // the chunk's rows [n][stride_w] 32-bit words
+  double* d_tab = nullptr;       // [n][4] tab, then k_bed_stats' lut [n][4], msd [n][2], counts [n][4]
+  double* d_beta = nullptr;      // [ncol][n] effects, then pk [n][16]
+  size_t S_cap = 0, part_cap = 0, rows_cap = 0, tab_cap = 0, beta_cap = 0;
+  // sgv_score_timers
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+  double ms = 0.0, chunks = 0.0, flops = 0.0, stage_ms = 0.0;
+};
+
 // launch tables of one LD matrix (rebuilt when a block's storage changes)
 // Strip tables of one MFMA strip kernel family over some of a plan's packed
 // blocks (build_strips): strips in dispatch order, their items in strip order,
@@ -440,6 +458,7 @@ struct sgv_ctx {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> gpending;   // exact-CG read gaps
   std::vector<std::pair<hipEvent_t, hipEvent_t>> empending;  // EM loops
   double xchg_n = 0.0, xchg_ms = 0.0, xchg_bytes = 0.0;
+  ScoreState score;
   std::string err;
 };
 

@@ -356,6 +356,59 @@ class Engine:
         """Free the staged genotypes and their tables."""
         self.ctx.sgv_geno_clear()
 
+    # ---- scoring a target panel (sgv_score_*) ---------------------------------
+    def score_begin(self, nsamp, ncol):
+        """Start a scoring stream over a target panel of nsamp samples for ncol
+        (1..hb.SCORE_MAXCOL) effect columns.  Needs no LD and leaves the LD, the
+        staged genotypes and the vectors of this engine alone."""
+        self.ctx.sgv_score_begin(int(nsamp), int(ncol))
+        self._score_shape = (int(nsamp), int(ncol))
+
+    def score_chunk(self, rows, beta, mode=hb.SCORE_TARGET, tab=None):
+        """Add the stream's next markers: rows (n, >= ceil(nsamp / 4)) uint8 .bed
+        rows, beta (ncol, n) effects, tab (n, 4) for mode hb.SCORE_TABLE.  Every
+        chunk but the last holds a multiple of 1,024 markers.  Returns the (n, 4)
+        int64 counts of the codes 0..3 per marker."""
+        rows = np.asarray(rows)
+        if rows.dtype != np.uint8 or rows.ndim != 2:
+            raise ValueError("score rows: %s %s, expected a 2-d uint8 array"
+                             % (rows.dtype, rows.shape))
+        rows = np.ascontiguousarray(rows)
+        n = rows.shape[0]
+        beta = hb.f64(beta)
+        if beta.ndim == 1:
+            beta = beta.reshape(1, -1)
+        if beta.ndim != 2 or beta.shape[1] != n:
+            raise ValueError("score effects: %s, expected (ncol, %d)" % (beta.shape, n))
+        ncol = getattr(self, "_score_shape", (0, beta.shape[0]))[1]
+        if beta.shape[0] != ncol:
+            raise ValueError("score effects: %d columns, the stream has %d" % (beta.shape[0], ncol))
+        tp = None
+        if tab is not None:
+            tab = hb.f64(tab)
+            if tab.shape != (n, 4):
+                raise ValueError("score tab: %s, expected (%d, 4)" % (tab.shape, n))
+            tp = hb.dptr(tab)
+        counts = np.empty((n, 4), dtype=np.int64)
+        self.ctx.sgv_score_chunk(rows.ctypes.data_as(hb._c_u8_p), int(rows.shape[1]), int(n),
+                                 int(mode), tp, hb.dptr(beta), int(n),
+                                 counts.ctypes.data_as(hb._c_i64_p))
+        return counts
+
+    def score_end(self):
+        """End the stream: (ncol, nsamp) scores."""
+        if not hasattr(self, "_score_shape"):
+            self.ctx.sgv_score_end(None)     # the library's refusal (no stream)
+        nsamp, ncol = self._score_shape
+        out = np.empty((ncol, nsamp), dtype=np.float64)
+        self.ctx.sgv_score_end(hb.dptr(out))
+        return out
+
+    def score_timers(self, reset=False):
+        t = np.zeros(hb.SCORE_TIMERS_N)
+        self.ctx.sgv_score_timers(hb.dptr(t), len(t), int(bool(reset)))
+        return dict(kernel_ms=t[0], chunks=int(t[1]), flops=t[2], stage_ms=t[3])
+
     # ---- hot path ------------------------------------------------------------
     def denoise(self, gam1s, a, lam, omegas, sigmas, rho, damp):
         out = np.zeros(self.K)

@@ -27,6 +27,10 @@ MAX_COHORTS = 1024
 MAX_SLABS = 8
 ABI_VERSION = 2          # the header's SGV_ABI_VERSION this binding is typed against
 TIMERS_N, EXCHANGE_STATS_N, COMM_INFO_N = 10, 16, 5
+# sgv_score_*: columns per stream, the table modes, the timers' length
+SCORE_MAXCOL = 64
+SCORE_TARGET, SCORE_RAW, SCORE_TABLE = 0, 1, 2
+SCORE_TIMERS_N = 4
 
 # sgv_ld_pass_form / sgv_pass_form_model (the header's SGV_KIND_*, SGV_PF_*, SGV_PS_*, SGV_SW_*,
 # in index order): the kinds by value, the form's fields, the shape's, the switches
@@ -100,6 +104,11 @@ _SIGS = {
     "sgv_geno_r": [_vp, ctypes.c_int, _c_dbl_p],
     "sgv_geno_g": [_vp, _c_dbl_p, _c_dbl_p],
     "sgv_geno_clear": [_vp],
+    "sgv_score_begin": [_vp, ctypes.c_int, ctypes.c_int],
+    "sgv_score_chunk": [_vp, _c_u8_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _c_dbl_p,
+                        _c_dbl_p, ctypes.c_int64, _c_i64_p],
+    "sgv_score_end": [_vp, _c_dbl_p],
+    "sgv_score_timers": [_vp, _c_dbl_p, ctypes.c_int, ctypes.c_int],
     "sgv_denoise": [_vp, _c_dbl_p, _c_dbl_p, ctypes.c_double, ctypes.c_int, _c_dbl_p, _c_dbl_p,
                     ctypes.c_double, ctypes.c_int, _c_dbl_p],
     "sgv_posterior": [_vp, _c_dbl_p, _c_dbl_p, ctypes.c_double, ctypes.c_int, _c_dbl_p, _c_dbl_p,
